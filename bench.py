@@ -21,7 +21,13 @@ bit-exact with the reference fixtures) over a spawn pool of host processes on th
 first frames of the same LLR batch; the C port (oracle/refcpu.c, OpenMP) beside it.
 
 info-Mbps = frames * K_info / t / 1e6 (throughput_test.py:217, :304).
-Usage: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full].
+A plain run sets up the headline's frames, warms up, times exactly K steps and
+prints the result line (no CPU pool, no secondary key, no detail file).  `--full`
+adds every secondary key above and the CPU baselines, as one run measured them
+before the option existed; `--sections` / `--skip-*` select among them.
+`--dump-outputs DIR` writes what the headline's last timed step left for its
+caller (see dump_outputs) as DIR/<name>.npy.  With N > 1 and no
 WORLD_SIZE in the environment, bench.py re-launches itself under
 torch.distributed.run with N ranks (before any GPU call).  `--cpu-stub` runs the
 same rank/timing/all-reduce path on CPU (gloo) with a stub decode: a plumbing
@@ -341,6 +347,30 @@ def decode_loop(rt, plan, llr, out, msg, width, steps, warmup, iters=None):
     return dt, per_rank, kt.mean_ms(), counts.cpu().numpy()
 
 
+DUMP_MAX_BYTES = 32 << 20  # decoded_bits.npy; the whole dump stays far below 64 MB
+
+
+def dump_outputs(path, out, counts):
+    """--dump-outputs: the arrays the headline's timed path hands its caller after
+    the last timed step.  decoded_bits.npy: the decoded info bits (float32, one row
+    per frame) of a fixed, seeded sample of this rank's frames when the whole
+    (B, K) matrix would exceed DUMP_MAX_BYTES; decoded_bits_frames.npy: the sampled
+    rows' frame indices within the rank's batch (float64, ascending);
+    error_counts.npy: the device counters {bit errors, frame errors, frames} over
+    the timed steps (float64).  The frames are a function of the arguments alone
+    (seeded Philox on global frame indices), so two builds run with the same
+    arguments can be compared array for array."""
+    os.makedirs(path, exist_ok=True)
+    B, K = out.shape
+    rows = min(B, max(1, DUMP_MAX_BYTES // (4 * K)))
+    idx = np.arange(B) if rows == B else np.sort(np.random.RandomState(20240).permutation(B)[:rows])
+    bits = out[torch.from_numpy(idx).to(out.device)].cpu().numpy().astype(np.float32)
+    np.save(os.path.join(path, "decoded_bits.npy"), bits)
+    np.save(os.path.join(path, "decoded_bits_frames.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "error_counts.npy"), np.asarray(counts, dtype=np.float64))
+    log("bench.py: outputs of the last timed step (%d of %d frames) in %s" % (rows, B, path))
+
+
 def _bench_headline(args, rt, pool, N, K, L, B):
     """BASELINE configs[1] decode (+ the end-to-end Monte-Carlo step)."""
     from polarcode_and_ldpc_amd import _native
@@ -349,6 +379,8 @@ def _bench_headline(args, rt, pool, N, K, L, B):
     plan = dec.plan
     out = torch.empty((B, K), dtype=torch.uint8, device="cuda")
     dt, per_rank, kms, c = decode_loop(rt, plan, llr, out, msg, K, args.steps, args.warmup)
+    if args.dump_outputs and rt.rank == 0:
+        dump_outputs(args.dump_outputs, out, c)
     res = dict(value=B * rt.world * args.steps * K / dt / 1e6, ms_per_step=dt / args.steps * 1e3,
                rank_ms_per_step=[t / args.steps * 1e3 for t in per_rank], kernel_ms=kms, B=B,
                roofline=roofline("polar_scl_1024_l8", polar_kernel_name(plan, 10), B, 8 * N + K, kms),
@@ -981,14 +1013,33 @@ def main():
                     help="only the headline decodes (no end-to-end / valid-codeword / configs[3,4] runs)")
     ap.add_argument("--sections", default=None,
                     help="comma list of " + ",".join(SECTIONS) + " (profiling passes: one kernel per section)")
-    ap.add_argument("--detail-out", default="gpurun_out/bench_detail.json",
-                    help="file for the full result (stdout carries one compact line); '' = none")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary key (end-to-end, other frozen sets / decoders / sizes, LDPC, "
+                         "CA-SCL + BER sweep, long blocks) and the CPU baselines; without it only the headline "
+                         "decode is set up, timed and reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline's decoded bits (a fixed sample of the frames) "
+                         "and error counters of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--detail-out", default=None,
+                    help="file for the full result (stdout carries one compact line); '' = none; "
+                         "default: bench_out/bench_detail.json with --full, none without")
     ap.add_argument("--cpu-stub", action="store_true", help="CPU/gloo plumbing check with a stub decode")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: host-side counter reduction, ranks may share one GPU (rehearsal only)")
     args = ap.parse_args()
     sec = set(SECTIONS) if args.sections is None else set(args.sections.split(","))
     assert sec <= set(SECTIONS), "unknown section in --sections"
+    if args.detail_out is None:
+        args.detail_out = "bench_out/bench_detail.json" if args.full else ""
+    if not args.full:
+        # a plain run: the headline decode alone (its roofline comes from the timed
+        # launches' own HIP events), no CPU pool
+        if args.sections is not None:
+            ap.error("--sections selects among the keys of a --full run: add --full")
+        sec = {"polar"}
+        args.skip_cpu = True
+    if args.dump_outputs and (args.cpu_stub or "polar" not in sec):
+        ap.error("--dump-outputs writes the headline decode's outputs: it needs the polar section and no --cpu-stub")
     if args.skip_extra:
         sec &= {"polar", "ldpc"}
     if args.skip_ldpc:
@@ -1061,8 +1112,9 @@ def main():
             # the contract times the CPU path on rank 0 at N = 1 only: the N = 1
             # line of the same build carries it (the host cores are shared by the
             # N ranks here, so a figure taken now would measure contention)
-            full["cpu_baseline_note"] = ("not measured: %s" % ("--skip-cpu" if args.skip_cpu else
-                                         "timed on rank 0 at N = 1 only (see the N = 1 line of this build)"))
+            full["cpu_baseline_note"] = ("not measured: %s" % (
+                "a plain run times the headline alone (--full adds it)" if not args.full else
+                "--skip-cpu" if args.skip_cpu else "timed on rank 0 at N = 1 only (see the N = 1 line of this build)"))
         path = write_detail(full, args.detail_out)
         print(json.dumps(compact_line(full, path)), flush=True)
     rt.close()

@@ -14,7 +14,8 @@ Fixture inventory:
                            order of benchmarks/throughput_test.py:196-228
                            (AWGNChannel(3.0, seed=42), 10 warm-up frames first);
                            plus SCL L=1/2/4/8 on the first 32 frames.
-  polar_sc_1024.npz    F2  SC N=1024 K=512, default + bit-reversed
+  polar_sc_1024_default.npz, polar_sc_1024_bhatta.npz
+                       F2  SC N=1024 K=512, default + bit-reversed
                            Bhattacharyya(2 dB) frozen sets, 0/1/3 dB.
   polar_scl_1024_l8.npz F3 SCL N=1024 K=512 L=8 (bit-reversed Bhattacharyya)
                            at 0/1.5/3 dB, and the default set at 3 dB.
@@ -144,12 +145,14 @@ def _polar_frames(N, K, frozen, snrs, frames, seed):
 
 
 def job_sc1024():
+    """One file per frozen set (the two together exceed 1 MiB)."""
     polar, _, _ = _imp()
     N, K = 1024, 512
-    out = dict(N=N, K=K)
+    files = []
     default_frozen, _ = polar.generate_frozen_bits(N, K)
     for tag, fr in (("default", np.asarray(default_frozen, np.int64)),
                     ("bhatta", bitrev_bhatta_frozen(N, K))):
+        out = dict(N=N, K=K)
         llr, msg, snr = _polar_frames(N, K, fr, (0.0, 1.0, 3.0), 24, 1000 + len(tag))
         dec = polar.SCDecoder(N, K, frozen_bits=fr)
         out[tag + "_frozen"] = fr
@@ -157,7 +160,8 @@ def job_sc1024():
         out[tag + "_msg"] = msg
         out[tag + "_snr"] = snr
         out[tag + "_sc"] = np.array([dec.decode(l) for l in llr])
-    return "polar_sc_1024.npz", out
+        files.append(("polar_sc_1024_%s.npz" % tag, out))
+    return files
 
 
 def job_scl(N, K, L, snrs, frames, seed, name, frozen_kind="bhatta"):
@@ -764,9 +768,11 @@ JOBS = [job_scl4096_l8, job_scl1024_l8, job_ms8192, job_scl1024_l32, job_bp504,
 
 def _run(fn):
     t = time.time()
-    name, out = fn()
-    np.savez_compressed(os.path.join(HERE, name), **out)
-    return name, time.time() - t
+    res = fn()
+    files = [res] if isinstance(res, tuple) else res  # a job may write several files
+    for name, out in files:
+        np.savez_compressed(os.path.join(HERE, name), **out)
+    return ", ".join(name for name, _ in files), time.time() - t
 
 
 def main():

@@ -41,6 +41,42 @@ def test_compact_line_fits_driver_tail():
     assert json.loads(s) == line
 
 
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: float32/float64 .npy files; an output above the byte budget is
+    cut to the same seeded, ascending sample of rows on every call."""
+    import numpy as np
+    import torch
+    B, K = 1000, 16
+    out = torch.from_numpy(np.random.RandomState(1).randint(0, 2, (B, K)).astype(np.uint8))
+    counts = np.array([5, 3, 2000], dtype=np.int64)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100 * 4 * K)
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dirs:
+        bench.dump_outputs(d, out, counts)
+    a, b = ({n: np.load(os.path.join(d, n)) for n in sorted(os.listdir(d))} for d in dirs)
+    assert sorted(a) == ["decoded_bits.npy", "decoded_bits_frames.npy", "error_counts.npy"]
+    for n in a:
+        assert a[n].dtype in (np.float32, np.float64) and np.array_equal(a[n], b[n]), n
+    idx = a["decoded_bits_frames.npy"].astype(np.int64)
+    assert idx.shape == (100,) and (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < B
+    assert a["decoded_bits.npy"].shape == (100, K) and a["decoded_bits.npy"].nbytes <= 100 * 4 * K
+    assert np.array_equal(a["decoded_bits.npy"], out.numpy()[idx].astype(np.float32))
+    assert np.array_equal(a["error_counts.npy"], [5.0, 3.0, 2000.0])
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", B * 4 * K)  # the whole output fits: no sampling
+    bench.dump_outputs(dirs[0], out, counts)
+    assert np.array_equal(np.load(os.path.join(dirs[0], "decoded_bits.npy")), out.numpy().astype(np.float32))
+    assert np.array_equal(np.load(os.path.join(dirs[0], "decoded_bits_frames.npy")), np.arange(B))
+
+
+def test_sections_need_full():
+    """Secondary keys are measured only behind --full: asking for one without it is an error."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sections", "ldpc"], capture_output=True,
+                       text=True, timeout=120, cwd=ROOT)
+    assert p.returncode == 2 and "--full" in p.stderr and p.stdout == ""
+
+
 def test_compact_line_survives_extra_ranks():
     """An 8-rank line (per-rank times) stays under the limit too."""
     full = _payload()

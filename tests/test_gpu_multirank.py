@@ -27,7 +27,7 @@ def _bench(args, tmp_path, timeout=300):
         env.pop(k, None)
     detail = str(tmp_path / "detail.json")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-                        "--skip-cpu", "--detail-out", detail] + args, capture_output=True, text=True,
+                        "--full", "--skip-cpu", "--detail-out", detail] + args, capture_output=True, text=True,
                        timeout=timeout, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -66,7 +66,7 @@ def test_scl_p1_frames(gpu, L):
 
 @pytest.mark.parametrize("tag", ["default", "bhatta"])
 def test_sc_1024(gpu, tag):
-    d = golden("polar_sc_1024.npz")
+    d = golden("polar_sc_1024_%s.npz" % tag)
     dec = _P().SCDecoder(1024, 512, frozen_bits=d[tag + "_frozen"])
     assert _mismatch(dec.decode_batch(d[tag + "_llr"]), d[tag + "_sc"]) == 0
 

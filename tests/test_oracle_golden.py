@@ -21,8 +21,8 @@ def test_p1_sc_and_scl(oracle):
 
 
 def test_sc_1024(oracle):
-    d = golden("polar_sc_1024.npz")
     for tag in ("default", "bhatta"):
+        d = golden("polar_sc_1024_%s.npz" % tag)
         assert _bad(oracle.sc_decode(1024, d[tag + "_frozen"], d[tag + "_llr"], threads=4), d[tag + "_sc"]) == 0
 
 

@@ -26,7 +26,7 @@ for G in ${GROUPS_TO_RUN:-g1 g2}; do
     g2) SECT="polar_default,sc_default,config0,long_ms,ldpc_valid" ;;
   esac
   OUT="$BASE/$G"; mkdir -p "$OUT"
-  ARGS="--skip-cpu --sections $SECT --long-batch 131072 --extra-steps 3"
+  ARGS="--full --skip-cpu --sections $SECT --long-batch 131072 --extra-steps 3"
   echo "$G start $(date)" >> "$BASE/progress.txt"
   timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
       python3 "$R/bench.py" $ARGS --steps 10 --warmup 2 > "$OUT/bench_trace.json" 2> "$OUT/trace.err" || exit $?

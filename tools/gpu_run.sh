@@ -1,8 +1,8 @@
 # One parameterised runner for GPU-box calls (replaces the round-3 one-off scripts):
 #   gpurun -- 'bash tools/gpu_run.sh <command> ...'      outputs under gpurun_out/
-#   full  <tag>                        -m gpu tests, smoke(), default bench.py      -> gpurun_out/full_<tag>/
+#   full  <tag>                        -m gpu tests, smoke(), bench.py --full       -> full_<tag>/ in the output folder
 #   tests <log> [pytest args]          pytest (default: tests -m gpu)                -> gpurun_out/<log>.log
-#   bench <log> [bench.py args]        bench.py (stdout line + detail file)         -> gpurun_out/<log>.json
+#   bench <log> [bench.py args]        bench.py (stdout line + detail file; pass --full for every key) -> <log>.json
 #   ab    <log> <cases> <reps> <lib[@VAR=VAL]>...   tools/ab.py A/B timing          -> gpurun_out/<log>.log
 #   prof  <tag> [group]                tools/gpu_profile.sh (rocprofv3 trace + PMC)  -> gpurun_out/prof_<tag>/
 # Every GPU step runs under its own timeout; the first failure ends the call.
@@ -20,7 +20,7 @@ full)
     rc=$?; echo "pytest rc=$rc $(date)" >> "$OUT/progress.txt"; [ $rc -eq 0 ] || exit $rc
     timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || exit $?
     echo "smoke ok $(date)" >> "$OUT/progress.txt"
-    timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 --detail-out "$OUT/bench_detail.json" \
+    timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 --detail-out "$OUT/bench_detail.json" \
         > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
     echo "bench ok $(date)" >> "$OUT/progress.txt"
     ;;

@@ -13,7 +13,7 @@ for L in "$@"; do
   export PL_LIB_PATH="$R/$L"
   for C in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 -s KILL 300 rocprofv3 --pmc $C --output-format csv -d "$BASE/${N}_$C" -o run -- \
-        python3 "$R/bench.py" --skip-cpu --sections "$SECT" --long-batch 131072 --steps 2 --warmup 0 \
+        python3 "$R/bench.py" --full --skip-cpu --sections "$SECT" --long-batch 131072 --steps 2 --warmup 0 \
         > "$BASE/${N}_$C.out" 2> "$BASE/${N}_$C.err" || exit $?
     echo "$N $C ok $(date)" >> "$BASE/progress.txt"
   done

@@ -7,7 +7,7 @@ TAG=${1:-probe}
 R="$GRAFT_REPO_ROOT"; OUT="$R/gpurun_out/stall_$TAG"; mkdir -p "$OUT"
 export TMPDIR=/tmp; cd /tmp
 SECT=${SECT:-polar,ldpc,cascl}
-ARGS="--skip-cpu --sections $SECT --extra-steps 2 --steps 2 --warmup 0"
+ARGS="--full --skip-cpu --sections $SECT --extra-steps 2 --steps 2 --warmup 0"
 timeout -k 10 -s KILL 60 rocprofv3 -L > "$OUT/counters.txt" 2>&1 || true
 P1="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS"
 i=0
