@@ -30,6 +30,8 @@ extern "C" {
 
 #define PL_LDPC_BP 0 /* BPDecoder: sum-product, tanh rule   (src/ldpc/decoder.py:11-205)  */
 #define PL_LDPC_MS 1 /* MSDecoder: (normalised) min-sum     (src/ldpc/decoder.py:208-355) */
+#define PL_LDPC_LMS 2 /* layered (row-serial) normalised min-sum, build-defined
+                         (pl_ldpc_layered_plan_create; no reference counterpart)   */
 
 typedef struct pl_plan pl_plan;
 
@@ -40,11 +42,18 @@ typedef struct {
     int32_t list_size;  /* polar: 0 = SC, >=1 = SCL list size                      */
     int32_t lds_bytes;  /* dynamic LDS per workgroup of the decode kernel          */
     int32_t fused_top;  /* polar: tree depths fused into the channel read (>=1)    */
-    int32_t frames_per_block; /* frames one workgroup decodes                     */
+    int32_t frames_per_block; /* frames one workgroup decodes: polar, frames per
+                           wavefront; flooding LDPC, 2 on the degree-grouped BP
+                           kernel's two-frame instance, else 1; layered LDPC,
+                           frames per workgroup (one wavefront each), 1 when a
+                           workgroup decodes one frame                             */
     int32_t reserved;   /* polar: kernel (4 tree, 3 lane, 6 single-workgroup exact);
                            LDPC: 2 register-cached, 7 register-cached BP with
                            degree-grouped check products, 1 generic,
-                           3 thread-per-check, 5 min-sum with compressed check state */
+                           3 thread-per-check, 5 min-sum with compressed check state,
+                           8 (3,6)-regular min-sum with rebuild-ready check state,
+                           9 layered min-sum with its state in LDS,
+                           10 layered min-sum with its state in the workspace       */
 } pl_plan_info;
 
 /* Polar SC / SCL plan.
@@ -93,6 +102,35 @@ int pl_ldpc_plan_create(int32_t m, int32_t n, const int32_t* row_ptr, const int3
                         int32_t algo, int32_t max_iter, int32_t early_stop, double normalization,
                         int32_t flags, pl_plan** out);
 
+/* Layered (row-serial) normalised min-sum plan.  Build-defined extension: the
+ *   reference has flooding decoders only.  H as for pl_ldpc_plan_create.  The
+ *   rows are visited layer by layer: layer l holds rows
+ *   layer_rows[layer_ptr[l] .. layer_ptr[l+1]) (host arrays, layer_ptr[n_layers+1],
+ *   layer_rows[m]).  All fp64:
+ *     P[v] = llr[v]; R[c][j] = 0
+ *     for it < max_iter: for each layer in order, for each row c of it (deg > 0):
+ *         q[j] = P[v_j] - R[c][j]
+ *         R[c][j] = (prod_{k != j} sign(q[k]) * min_{k != j} |q[k]|) * normalization
+ *                   (MSDecoder._check_node_update_ms on q, NumPy special values)
+ *         P[v_j] = q[j] + R[c][j]
+ *       decoded = P <= 0; with early_stop, stop once H decoded = 0 (iterations = it + 1)
+ *   max_iter == 0 returns the decisions of the channel LLRs, iterations 0.
+ *   PL_EINVAL unless the layers list every row exactly once and no two rows of a
+ *   layer share a column; PL_EUNSUPPORTED for a degree-1 row when max_iter > 0
+ *   (empty minimum; with max_iter == 0 no check is evaluated, as in MSDecoder)
+ *   or a row degree >= 2048.  Every argument check runs before the first device call.
+ *   One thread updates one check; a code whose largest layer has <= 64 rows runs
+ *   one wavefront per frame (several frames per workgroup), others one workgroup
+ *   per frame.  The per-frame state (P and the compressed check state, about
+ *   8 n + 20 m bytes) lives in LDS when it fits 160 KB (pl_plan_info.reserved
+ *   9), else in the workspace (10); PL_LMS_GLOBAL=1 at plan creation forces the
+ *   workspace (diagnostic).  pl_decode, pl_decode_ws, pl_plan_workspace_bytes,
+ *   pl_plan_reserve and pl_plan_release work as for any plan. */
+int pl_ldpc_layered_plan_create(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                                int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_rows,
+                                int32_t max_iter, int32_t early_stop, double normalization, int32_t flags,
+                                pl_plan** out);
+
 /* Batched decode: replaces SCDecoder.decode (decoder.py:38-71),
  *   SCLDecoder.decode (:225-262), BPDecoder.decode (src/ldpc/decoder.py:124-202)
  *   and MSDecoder.decode (:289-352) applied to `batch` frames.
@@ -126,6 +164,15 @@ int pl_plan_workspace_bytes(const pl_plan* plan, int64_t batch, int64_t* bytes);
 int pl_decode_ws(pl_plan* plan, const double* llr_dev, int64_t batch, int64_t ld, uint8_t* bits_dev,
                  int32_t* iters_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
 
+/* pl_decode of a layered min-sum plan that also writes the final posteriors
+ * P (the state the decisions are taken from: bits = P <= 0) to post_dev, fp64
+ * [batch][ld_post] device, ld_post >= n.  Bits, iteration counts and posteriors
+ * are reproducible bit for bit (no transcendental is involved; NaN payloads
+ * and the sign of a zero are unspecified).  PL_EUNSUPPORTED for every other
+ * plan kind.  Workspace as pl_decode. */
+int pl_ldpc_decode_soft(pl_plan* plan, const double* llr_dev, int64_t batch, int64_t ld, uint8_t* bits_dev,
+                        int32_t* iters_dev, double* post_dev, int64_t ld_post, void* stream);
+
 /* Pre-allocate `stream`'s workspace for batches up to max_batch, so that
  * pl_decode on that stream never allocates (max_batch == 0: pl_plan_release).
  * If the device cannot hold the full-speed size, the largest halving of at
@@ -155,7 +202,7 @@ int pl_plan_destroy(pl_plan* plan);
 const char* pl_last_error(void);
 
 /* Calls that touch a plan's device memory -- pl_decode, pl_decode_ws,
- * pl_plan_reserve, pl_plan_release, pl_polar_plan_set_crc, pl_polar_encode,
+ * pl_ldpc_decode_soft, pl_plan_reserve, pl_plan_release, pl_polar_plan_set_crc, pl_polar_encode,
  * pl_debug_polar_stamps -- must run with the plan's device current (the device
  * current at plan creation); otherwise they return PL_EINVAL and do nothing.
  * pl_plan_get_info, pl_plan_workspace_bytes and pl_plan_workspace_stats read

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PL_LIB_PATH", os.path.join(_HERE, "_lib", "libpolarldpc.so"))
 
 PL_OK, PL_EINVAL, PL_ENOMEM, PL_EHIP, PL_EUNSUPPORTED = 0, -1, -2, -3, -4
-PL_LDPC_BP, PL_LDPC_MS = 0, 1
+PL_LDPC_BP, PL_LDPC_MS, PL_LDPC_LMS = 0, 1, 2
 
 EXPORTS = (
     "pl_polar_plan_create", "pl_ldpc_plan_create", "pl_decode", "pl_plan_reserve", "pl_plan_get_info",
@@ -25,7 +25,7 @@ EXPORTS = (
     "pl_count_errors", "pl_debug_polar_stamps", "pl_debug_ldpc_stamps", "pl_debug_polar_deadstore", "pl_polar_plan_set_crc", "pl_crc_append",
     "pl_rayleigh_llr", "pl_bsc", "pl_gf2_encode", "pl_decode_ws", "pl_plan_workspace_bytes",
     "pl_plan_release", "pl_plan_workspace_stats", "pl_debug_set_plan_device", "pl_debug_polar_fpw",
-    "pl_debug_polar_flagged", "pl_polar_plan_small_batch",
+    "pl_debug_polar_flagged", "pl_polar_plan_small_batch", "pl_ldpc_layered_plan_create", "pl_ldpc_decode_soft",
 )
 
 
@@ -46,6 +46,8 @@ def _load(path=LIB_PATH):
     PP = ctypes.POINTER(ctypes.c_void_p)
     L.pl_polar_plan_create.argtypes = [I32, I32, P, I32, I32, PP]
     L.pl_ldpc_plan_create.argtypes = [I32, I32, P, P, I32, I32, I32, D, I32, PP]
+    L.pl_ldpc_layered_plan_create.argtypes = [I32, I32, P, P, I32, P, P, I32, I32, D, I32, PP]
+    L.pl_ldpc_decode_soft.argtypes = [P, P, I64, I64, P, P, P, I64, P]
     L.pl_decode.argtypes = [P, P, I64, I64, P, P, P]
     L.pl_plan_reserve.argtypes = [P, I64, P]
     L.pl_decode_ws.argtypes = [P, P, I64, I64, P, P, P, I64, P]
@@ -202,6 +204,20 @@ class Plan:
                                    ctypes.c_void_p(bits.data_ptr()), it, ctypes.c_void_p(ws.data_ptr()),
                                    ws.numel() * ws.element_size(), st), "pl_decode_ws")
 
+    def decode_soft(self, llr: "torch.Tensor", bits: "torch.Tensor", iters: "torch.Tensor | None",
+                    post: "torch.Tensor", stream=None):
+        """decode() of a layered min-sum plan that also writes the posterior LLRs:
+        post fp64 [B, >=n] device with unit inner stride (pl_ldpc_decode_soft).
+        Any other plan kind raises ValueError."""
+        self._check(llr, bits, iters)
+        assert post.is_cuda and post.dtype == torch.float64 and post.dim() == 2 and post.stride(1) == 1 \
+            and post.shape[0] == llr.shape[0] and post.shape[1] >= self.info.n_in, \
+            "post must be a float64 [B, >=n] device tensor with unit inner stride"
+        it = ctypes.c_void_p(iters.data_ptr()) if iters is not None else None
+        check(lib.pl_ldpc_decode_soft(self._h, ctypes.c_void_p(llr.data_ptr()), llr.shape[0], _ld(llr),
+                                      ctypes.c_void_p(bits.data_ptr()), it, ctypes.c_void_p(post.data_ptr()),
+                                      _ld(post), ctypes.c_void_p(_stream(stream))), "pl_ldpc_decode_soft")
+
     def decode_stamped(self, llr: "torch.Tensor", bits: "torch.Tensor", stamps: "torch.Tensor", stream=None):
         """Diagnostic decode accumulating per-phase cycle totals into stamps (int64 [5])."""
         check(lib.pl_debug_polar_stamps(self._h, ctypes.c_void_p(llr.data_ptr()), llr.shape[0], _ld(llr),
@@ -250,6 +266,26 @@ def ldpc_plan(row_ptr: np.ndarray, col_idx: np.ndarray, n: int, algo: int, max_i
                                   ci.ctypes.data_as(ctypes.c_void_p), int(algo), int(max_iter),
                                   int(bool(early_stop)), float(normalization), 0, ctypes.byref(h)),
           "pl_ldpc_plan_create")
+    return Plan(h)
+
+
+def layered_ldpc_plan(row_ptr: np.ndarray, col_idx: np.ndarray, n: int, layers, max_iter: int, early_stop: bool,
+                      normalization: float = 1.0) -> Plan:
+    """Layered min-sum plan (pl_ldpc_layered_plan_create); layers: a sequence of
+    row-index sequences, visited in that order."""
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int32)
+    ci = np.ascontiguousarray(col_idx, dtype=np.int32)
+    lp = np.zeros(len(layers) + 1, dtype=np.int32)
+    lp[1:] = np.cumsum([len(l) for l in layers])
+    lr = np.ascontiguousarray(np.concatenate([np.asarray(l, dtype=np.int32).ravel() for l in layers])
+                              if len(layers) else np.zeros(0, np.int32), dtype=np.int32)
+    require_gpu()
+    h = ctypes.c_void_p()
+    check(lib.pl_ldpc_layered_plan_create(len(rp) - 1, int(n), rp.ctypes.data_as(ctypes.c_void_p),
+                                          ci.ctypes.data_as(ctypes.c_void_p), len(layers),
+                                          lp.ctypes.data_as(ctypes.c_void_p), lr.ctypes.data_as(ctypes.c_void_p),
+                                          int(max_iter), int(bool(early_stop)), float(normalization), 0,
+                                          ctypes.byref(h)), "pl_ldpc_layered_plan_create")
     return Plan(h)
 
 

@@ -64,6 +64,10 @@ struct pl_plan {
     pl::LdpcDev ld{};
     int32_t* d_ldpc = nullptr;
     int64_t ldpc_chunk = 16384;  // frames per launch of the global-workspace kernel
+    // layered min-sum (ldpc_layered.hip): kind 1 with its own geometry; lg.n is set too
+    bool layered = false;
+    pl::LmsGeom lms{};
+    pl::LmsDev lmsd{};
     // workspace: bytes per unit (polar: one resident wave; LDPC global: one
     // frame), one buffer per stream (plans are shared across host threads that
     // use distinct streams; a decode only ever touches its stream's buffer)
@@ -607,6 +611,86 @@ extern "C" int pl_ldpc_plan_create(int32_t m, int32_t n, const int32_t* row_ptr,
     return PL_OK;
 }
 
+extern "C" int pl_ldpc_layered_plan_create(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                                           int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_rows,
+                                           int32_t max_iter, int32_t early_stop, double normalization, int32_t flags,
+                                           pl_plan** out) {
+    (void)flags;
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    *out = nullptr;
+    // every argument check comes before the first device call
+    if (m < 0 || n < 1 || !row_ptr || (!col_idx && row_ptr[m] > 0)) return fail(PL_EINVAL, "bad H");
+    if (max_iter < 0) return fail(PL_EINVAL, "max_iter must be >= 0");
+    const int E = row_ptr[m];
+    if (row_ptr[0] != 0 || E < 0) return fail(PL_EINVAL, "row_ptr[0] must be 0");
+    // row_ptr monotone and within [0, E] before any col_idx entry is read
+    for (int c = 0; c < m; ++c)
+        if (row_ptr[c + 1] < row_ptr[c] || row_ptr[c + 1] > E) return fail(PL_EINVAL, "row_ptr not monotone");
+    int maxdc = 0;
+    bool deg1 = false;
+    for (int c = 0; c < m; ++c) {
+        const int d = row_ptr[c + 1] - row_ptr[c];
+        maxdc = std::max(maxdc, d);
+        deg1 |= d == 1;
+        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) {
+            if (col_idx[e] < 0 || col_idx[e] >= n) return fail(PL_EINVAL, "column index out of range");
+            if (e > row_ptr[c] && col_idx[e] <= col_idx[e - 1]) return fail(PL_EINVAL, "columns must ascend");
+        }
+    }
+    if (n_layers < 0 || !layer_ptr || (m > 0 && !layer_rows) || layer_ptr[0] != 0 || layer_ptr[n_layers] != m)
+        return fail(PL_EINVAL, "layers must list every row exactly once");
+    int max_layer = 0;
+    {
+        std::vector<uint8_t> seen((size_t)m, 0);
+        std::vector<int32_t> mark((size_t)n, -1);  // last layer that touched the column
+        for (int l = 0; l < n_layers; ++l) {
+            if (layer_ptr[l + 1] < layer_ptr[l] || layer_ptr[l + 1] > m)
+                return fail(PL_EINVAL, "layer_ptr not monotone");
+            max_layer = std::max(max_layer, layer_ptr[l + 1] - layer_ptr[l]);
+            for (int k = layer_ptr[l]; k < layer_ptr[l + 1]; ++k) {
+                const int c = layer_rows[k];
+                if (c < 0 || c >= m) return fail(PL_EINVAL, "layer row index out of range");
+                if (seen[c]) return fail(PL_EINVAL, "layers must list every row exactly once (row " + std::to_string(c) + " repeats)");
+                seen[c] = 1;
+                for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) {
+                    if (mark[col_idx[e]] == l)
+                        return fail(PL_EINVAL, "two rows of layer " + std::to_string(l) + " share column " +
+                                                   std::to_string(col_idx[e]));
+                    mark[col_idx[e]] = l;
+                }
+            }
+        }
+        // layer_ptr[n_layers] == m entries, none repeated, all in range: every row is listed
+    }
+    // max_iter == 0 evaluates no check (MSDecoder raises only once an iteration runs)
+    if (deg1 && max_iter > 0) return fail(PL_EUNSUPPORTED, "min-sum on a degree-1 check (reference raises ValueError)");
+    if (maxdc >= (1 << 11)) return fail(PL_EUNSUPPORTED, "check degree >= 2048");
+    pl_plan* p = new pl_plan();
+    p->kind = 1;
+    p->layered = true;
+    hipGetDevice(&p->device);
+    p->lg.n = n; p->lg.m = m; p->lg.E = E;
+    pl::LmsGeom& g = p->lms;
+    g.m = m; g.n = n; g.E = E; g.max_iter = max_iter; g.early_stop = early_stop ? 1 : 0; g.maxdc = maxdc;
+    g.n_layers = n_layers; g.max_layer = max_layer; g.norm = normalization;
+    pl::lms_geom(&g, env_int("PL_LMS_GLOBAL", 0) != 0);
+    std::vector<int32_t> all(row_ptr, row_ptr + m + 1);
+    all.insert(all.end(), col_idx, col_idx + E);
+    all.insert(all.end(), layer_ptr, layer_ptr + n_layers + 1);
+    all.insert(all.end(), layer_rows, layer_rows + m);
+    hipError_t e = upload(&p->d_ldpc, all);
+    if (e != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "plan upload"); }
+    p->lmsd.row_ptr = p->d_ldpc;
+    p->lmsd.col_idx = p->lmsd.row_ptr + (m + 1);
+    p->lmsd.layer_ptr = p->lmsd.col_idx + E;
+    p->lmsd.layer_rows = p->lmsd.layer_ptr + (n_layers + 1);
+    if ((e = pl::lms_prepare(g)) != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "hipFuncSetAttribute"); }
+    p->ws_unit = g.use_global ? (size_t)g.state_bytes : 0;
+    p->ldpc_chunk = std::max(1, env_int("PL_LDPC_CHUNK", 16384));
+    *out = p;
+    return PL_OK;
+}
+
 // Polar workspace layout for a grid of `grid` resident wavefronts: a list
 // plan's NaN masks first (for its largest grid, so they stay in place, and
 // zero, from one decode to the next), then the tree / lane kernel's frame-group
@@ -643,12 +727,32 @@ struct DecodeDiag {
     uint8_t* flagged = nullptr;
 };
 
+// Layered min-sum decode; post (fp64 [batch][ld_post]) may be null.  LDS-resident
+// state: launches below the grid limit; workspace-resident: chunks of the frames
+// the workspace holds (one state slice per frame of a chunk).
+static int lms_decode_impl(pl_plan* p, const double* llr, int64_t batch, int64_t ld, uint8_t* bits, int32_t* iters,
+                           double* post, int64_t ld_post, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (p->ws_unit > 0 && (ws == nullptr || ws_bytes < p->ws_unit))
+        return fail(PL_EINVAL, "workspace smaller than one unit (pl_plan_workspace_bytes)");
+    const int64_t step = p->ws_unit > 0 ? std::min<int64_t>(p->ldpc_chunk, (int64_t)(ws_bytes / p->ws_unit))
+                                        : kMaxLaunchItems / 1024;
+    for (int64_t b0 = 0; b0 < batch; b0 += step) {
+        const int64_t nb = std::min<int64_t>(step, batch - b0);
+        hipError_t e = pl::lms_launch(p->lms, p->lmsd, llr + b0 * ld, ld, bits + b0 * p->lms.n,
+                                      iters ? iters + b0 : nullptr, post ? post + b0 * ld_post : nullptr, ld_post, nb,
+                                      (unsigned char*)ws, s);
+        if (e != hipSuccess) return hipfail(e, "layered ldpc decode launch");
+    }
+    return PL_OK;
+}
+
 // Decode with an explicit workspace of ws_bytes (>= one unit when one is needed):
 // the polar grid / LDPC chunk is clamped to what the workspace holds.
 static int decode_impl(pl_plan* p, const double* llr, int64_t batch, int64_t ld, uint8_t* bits, int32_t* iters,
                        void* ws, size_t ws_bytes, hipStream_t s, bool zero_masks = false,
                        const DecodeDiag& dg = DecodeDiag()) {
     unsigned long long* const stamps = dg.stamps;
+    if (p->layered) return lms_decode_impl(p, llr, batch, ld, bits, iters, nullptr, 0, ws, ws_bytes, s);
     const size_t wmin = ws_min(p);
     if (wmin > 0 && (ws == nullptr || ws_bytes < wmin))
         return fail(PL_EINVAL, "workspace smaller than one unit (pl_plan_workspace_bytes)");
@@ -887,6 +991,25 @@ extern "C" int pl_decode_ws(pl_plan* p, const double* llr, int64_t batch, int64_
                        true);
 }
 
+extern "C" int pl_ldpc_decode_soft(pl_plan* p, const double* llr, int64_t batch, int64_t ld, uint8_t* bits,
+                                   int32_t* iters, double* post, int64_t ld_post, void* stream) {
+    if (!p) return fail(PL_EINVAL, "plan is NULL");
+    if (!p->layered) return fail(PL_EUNSUPPORTED, "posterior output: layered min-sum plans only");
+    int rc = check_decode_args(p, batch, ld, llr, bits);
+    if (rc) return rc;
+    if (batch > 0 && !post) return fail(PL_EINVAL, "NULL buffer");
+    if (ld_post < p->lms.n) return fail(PL_EINVAL, "ld_post < n");
+    if (batch == 0) return PL_OK;
+    if ((rc = check_device(p))) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    const size_t need = ws_need(p, batch);
+    if (!need) return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, nullptr, 0, s);
+    std::shared_ptr<Workspace> w = stream_entry(p, s);
+    std::lock_guard<std::mutex> lk(w->mu);
+    if ((rc = grow_ws(p, w.get(), s, need, false))) return rc;
+    return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, w->ptr, w->bytes, s);
+}
+
 extern "C" int pl_debug_polar_stamps(pl_plan* p, const double* llr, int64_t batch, int64_t ld, uint8_t* bits,
                                      unsigned long long* stamps_dev, void* stream) {
     if (!p || p->kind != 0 || !stamps_dev) return fail(PL_EINVAL, "polar plan and stamp buffer required");
@@ -1034,6 +1157,10 @@ extern "C" int pl_plan_get_info(const pl_plan* p, pl_plan_info* info) {
         info->lds_bytes = p->pg.lds_bytes; info->fused_top = p->pg.F;
         info->frames_per_block = p->fpw;
         info->reserved = p->generic ? 6 : (p->tree ? 4 : 3);  // kernel: 4 tree, 3 lane, 6 single-workgroup exact
+    } else if (p->layered) {
+        info->kind = 1; info->n_in = p->lms.n; info->n_out = p->lms.n; info->list_size = 0;
+        info->lds_bytes = p->lms.lds_bytes; info->fused_top = 0; info->frames_per_block = p->lms.fpb;
+        info->reserved = p->lms.use_global ? 10 : 9;  // layered min-sum: 9 state in LDS, 10 in the workspace
     } else {
         info->kind = 1; info->n_in = p->lg.n; info->n_out = p->lg.n; info->list_size = 0;
         info->lds_bytes = p->lg.lds_bytes; info->fused_top = 0; info->frames_per_block = p->lg.fpg > 1 ? p->lg.fpg : 1;

@@ -169,4 +169,29 @@ int ldpc_reg_ept(int variant);                // edges per thread of an ldpc_reg
 int ldpc_reg_vpt(int variant);                // variables per thread
 int ldpc_ms36_lds(int n);                     // LDS of the ldpc_ms36_kernel instance for n (0: none)
 
+// ---- layered min-sum (ldpc_layered.hip) ----
+struct LmsGeom {
+    int m, n, E, max_iter, early_stop, maxdc;
+    int n_layers, max_layer;  // layers and the checks of the largest one
+    double norm;
+    int mw;                   // meta words per check (1: every degree <= 16)
+    int wave;                 // 1: one wavefront per frame (max_layer <= 64); 0: one workgroup per frame
+    int use_global;           // state in the workspace instead of LDS
+    int fpb;                  // frames per workgroup
+    int threads, lds_bytes;
+    int64_t state_bytes;      // per frame: P[n] f64, then at off_mm [m] double2, at off_meta [m][mw] u32
+    int64_t off_mm, off_meta;
+};
+struct LmsDev {
+    const int32_t* row_ptr;     // [m+1]  H as given (original row order)
+    const int32_t* col_idx;     // [E]
+    const int32_t* layer_ptr;   // [n_layers+1]
+    const int32_t* layer_rows;  // [m]    rows layer by layer
+};
+void lms_geom(LmsGeom* g, bool force_global);
+hipError_t lms_prepare(const LmsGeom& g);
+// post: fp64 [batch][ld_post] posteriors or null; work: [batch] state slices (use_global) or null
+hipError_t lms_launch(const LmsGeom& g, const LmsDev& d, const double* llr, int64_t ld, uint8_t* bits, int32_t* iters,
+                      double* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
+
 }  // namespace pl

@@ -249,7 +249,8 @@ def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None)
 
 
 def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encoder=None):
-    """Round function for BPDecoder/MSDecoder.
+    """Round function for BPDecoder / MSDecoder / LayeredMSDecoder (any decoder
+    with `.plan`, `.n` and `.m`).
 
     encoder None: the all-zero codeword (BP and min-sum are codeword-symmetric);
     errors over the first `info_bits` positions, like ber_simulation.py:265-269

@@ -3,6 +3,8 @@
 Same constructors, attributes and `.decode(llr)` contract as the reference's
 src/ldpc/decoder.py (BPDecoder :11-205, MSDecoder :208-355), plus
 `decode_batch` for host or device batches.  No CPU path.
+LayeredMSDecoder (ldpc_layered.hip) is a build-defined extension: the serial
+schedule with posterior LLR output.
 """
 from __future__ import annotations
 
@@ -12,7 +14,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from .matrix import dense_to_csr
+from .matrix import dense_to_csr, layer_schedule
 
 
 class _LdpcBase:
@@ -108,3 +110,96 @@ class MSDecoder(_LdpcBase):
 
     def __repr__(self) -> str:
         return f"MSDecoder(n={self.n}, m={self.m}, max_iter={self.max_iter}, norm={self.normalization})"
+
+
+class LayeredMSDecoder(_LdpcBase):
+    """Layered (row-serial) normalised min-sum decoder with posterior LLR output
+    (ldpc_layered.hip).  Build-defined: the reference has flooding decoders only.
+
+    The rows of H are visited layer by layer, each check updating the posteriors
+    of its variables at once (MSDecoder's check rule on q = P - R), which
+    converges in about half the iterations of the flooding schedule.  `layers`:
+    a sequence of row-index sequences that lists every row once and whose rows
+    share no column within a layer (default: layer_schedule(H));
+    `[[c] for c in range(m)]` is the classic serial schedule."""
+
+    def __init__(self, H: np.ndarray, max_iter: int = 50, normalization: float = 1.0, early_stop: bool = True,
+                 layers=None):
+        self._algo = _native.PL_LDPC_LMS
+        self.normalization = normalization
+        self._setup(H, max_iter, early_stop)
+        self.layers = [np.asarray(l, dtype=np.int64).ravel() for l in (layer_schedule(H) if layers is None else layers)]
+
+    @property
+    def plan(self):
+        if self._plan is None:
+            self._plan = _native.layered_ldpc_plan(self._row_ptr, self._col_idx, self.n, self.layers, self.max_iter,
+                                                   self.early_stop, self.normalization)
+        return self._plan
+
+    def _check_runnable(self):
+        # as MSDecoder: np.min over the other inputs of a degree-1 check is an empty reduction
+        if self.max_iter > 0 and np.any(self.check_degrees == 1):
+            raise ValueError("zero-size array to reduction operation minimum which has no identity")
+
+    def _run_soft(self, llr, out=None):
+        """Device batch: llr fp64 [B, >=n] -> (bits uint8 [B, n], iters int32 [B], posterior fp64 [B, n])."""
+        self._check_runnable()
+        B = llr.shape[0]
+        if out is None:
+            out = torch.empty((B, self.n), dtype=torch.uint8, device=llr.device)
+        iters = torch.empty((B,), dtype=torch.int32, device=llr.device)
+        post = torch.empty((B, self.n), dtype=torch.float64, device=llr.device)
+        if B > 0:
+            self.plan.decode_soft(llr, out, iters, post)
+        return out, iters, post
+
+    def decode_batch(self, llr, out: Optional[torch.Tensor] = None, return_iterations: bool = False,
+                     return_llr: bool = False):
+        """Bits [B, n]; with return_iterations / return_llr also the iteration
+        counts and the posterior LLRs, in the order bits, iterations, posterior.
+        A CUDA tensor in gives CUDA tensors out (no host copy; `out`: a uint8
+        [B, n] device tensor for the bits); NumPy in gives int64 / float64 NumPy
+        out (`out`: an int64 [B, n] array for the bits)."""
+
+        def pick(bits, its, post):
+            r = (bits,) + ((its,) if return_iterations else ()) + ((post,) if return_llr else ())
+            return r if len(r) > 1 else bits
+
+        if isinstance(llr, torch.Tensor) and llr.is_cuda:
+            assert llr.dim() == 2 and llr.shape[1] == self.n, "LLR length must be %d" % self.n
+            if llr.dtype != torch.float64 or llr.stride(1) != 1:
+                llr = llr.to(torch.float64).contiguous()
+            if return_llr:
+                return pick(*self._run_soft(llr, out))
+            bits, its = self._run(llr, out)
+            return pick(bits, its, None)
+        a = np.asarray(llr.cpu().numpy() if isinstance(llr, torch.Tensor) else llr, dtype=np.float64)
+        assert a.ndim == 2 and a.shape[1] == self.n, "LLR length must be %d" % self.n
+        if a.shape[0] == 0:
+            self._check_runnable()
+            bits = np.zeros((0, self.n), dtype=np.int64) if out is None else out
+            return pick(bits, np.zeros(0, dtype=np.int64), np.zeros((0, self.n), dtype=np.float64))
+        _native.require_gpu()
+        dev = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        if return_llr:
+            bits, its, post = self._run_soft(dev)
+            post = post.cpu().numpy()
+        else:
+            (bits, its), post = self._run(dev), None
+        b = bits.cpu().numpy().astype(np.int64)
+        if out is not None:
+            out[...] = b
+            b = out
+        return pick(b, its.cpu().numpy().astype(np.int64), post)
+
+    def decode(self, llr: np.ndarray, return_iterations: bool = False):
+        assert len(llr) == self.n, f"LLR length must be {self.n}"
+        bits, its = self.decode_batch(np.asarray(llr, dtype=np.float64)[None, :], return_iterations=True)
+        if return_iterations:
+            return bits[0], int(its[0])
+        return bits[0]
+
+    def __repr__(self) -> str:
+        return (f"LayeredMSDecoder(n={self.n}, m={self.m}, max_iter={self.max_iter}, norm={self.normalization}, "
+                f"layers={len(self.layers)})")

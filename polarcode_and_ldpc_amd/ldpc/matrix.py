@@ -30,6 +30,29 @@ def csr_to_dense(row_ptr, col_idx, n: int) -> np.ndarray:
     return H
 
 
+def layer_schedule(H: np.ndarray) -> list:
+    """Layers for LayeredMSDecoder: a first-fit colouring of the rows in row
+    order.  Row c joins the lowest-numbered layer that holds no row sharing a
+    column with c (layers numbered in order of creation), so the rows of a layer
+    are variable-disjoint and zero-degree rows land in layer 0.  Returns a list
+    of int arrays (ascending row indices)."""
+    row_ptr, col_idx = dense_to_csr(H)
+    used = []    # per layer: bool [n], columns taken by its rows
+    layers = []
+    for c in range(len(row_ptr) - 1):
+        cols = col_idx[row_ptr[c]:row_ptr[c + 1]]
+        for l, u in enumerate(used):
+            if not u[cols].any():
+                break
+        else:
+            l = len(used)
+            used.append(np.zeros(np.asarray(H).shape[1], dtype=bool))
+            layers.append([])
+        used[l][cols] = True
+        layers[l].append(c)
+    return [np.asarray(l, dtype=np.int64) for l in layers]
+
+
 def mackay_construction(n: int, k: int, dv: int, dc: int, seed: Optional[int] = None) -> np.ndarray:
     m = n - k
     if dv * n != dc * m:
