@@ -262,6 +262,45 @@ int pl_debug_polar_flagged(pl_plan* plan, const double* llr_dev, int64_t batch, 
  * the wrong-device protection off for that plan. */
 int pl_debug_set_plan_device(pl_plan* plan, int32_t device);
 
+/* What the host-side LDPC planner (csrc/ldpc_plan.cpp) decides for a code,
+ * without creating a plan: no device call, so it runs on a machine without a
+ * GPU.  Product and diagnostic builds.  Arguments as pl_ldpc_plan_create (same
+ * checks, codes and messages), with the planning switches given explicitly
+ * instead of read from the environment: kernel_override one of
+ * PL_LDPC_KERNEL_* (PL_LDPC_KERNEL; CHECK counts in the diagnostic build only),
+ * bp_fpg the PL_BP_FPG value (0: the kernel's default, 1, anything else 2),
+ * lms_global the PL_LMS_GLOBAL flag (layered plans only). */
+#define PL_LDPC_KERNEL_DEFAULT 0
+#define PL_LDPC_KERNEL_GENERIC 1
+#define PL_LDPC_KERNEL_REG 2
+#define PL_LDPC_KERNEL_COMPACT 3
+#define PL_LDPC_KERNEL_CHECK 4
+typedef struct {
+    int32_t kernel;      /* the pl_plan_info.reserved code the plan would report */
+    int32_t threads, lds_bytes, use_global, reg_variant, grp, fpg, tl, npad, compact, ms36;
+    int64_t work_bytes_per_frame;
+    int64_t table_len;   /* int32 elements of the plan's one device table buffer   */
+    int64_t grp_at, ms_vw_at; /* element offsets of the degree-grouped BP tables and
+                            of the (3,6) min-sum address words in it             */
+    uint64_t digest;     /* 64-bit FNV-1a over the buffer's bytes                  */
+} pl_ldpc_plan_probe;
+int pl_debug_ldpc_plan_probe(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx, int32_t algo,
+                             int32_t max_iter, int32_t early_stop, double normalization, int32_t kernel_override,
+                             int32_t bp_fpg, int32_t lms_global, pl_ldpc_plan_probe* out);
+/* The same for pl_ldpc_layered_plan_create: the layered kernel's geometry. */
+typedef struct {
+    int32_t kernel;      /* 9 or 10, as pl_plan_info.reserved */
+    int32_t maxdc, n_layers, max_layer, mw, wave, use_global, fpb, threads, lds_bytes;
+    int64_t state_bytes, off_mm, off_meta;
+    int64_t table_len;
+    uint64_t digest;
+} pl_ldpc_layered_plan_probe;
+int pl_debug_ldpc_layered_plan_probe(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                                     int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_rows,
+                                     int32_t max_iter, int32_t early_stop, double normalization,
+                                     int32_t kernel_override, int32_t bp_fpg, int32_t lms_global,
+                                     pl_ldpc_layered_plan_probe* out);
+
 /* ---- Monte-Carlo frame source (replaces src/channel/awgn.py:91-112 and the
  *      message/encode loop of benchmarks/ber_simulation.py:167-177) ---------- */
 

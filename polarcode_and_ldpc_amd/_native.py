@@ -26,6 +26,7 @@ EXPORTS = (
     "pl_rayleigh_llr", "pl_bsc", "pl_gf2_encode", "pl_decode_ws", "pl_plan_workspace_bytes",
     "pl_plan_release", "pl_plan_workspace_stats", "pl_debug_set_plan_device", "pl_debug_polar_fpw",
     "pl_debug_polar_flagged", "pl_polar_plan_small_batch", "pl_ldpc_layered_plan_create", "pl_ldpc_decode_soft",
+    "pl_debug_ldpc_plan_probe", "pl_debug_ldpc_layered_plan_probe",
 )
 
 
@@ -33,6 +34,22 @@ class PlanInfo(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("n_in", ctypes.c_int32), ("n_out", ctypes.c_int32),
                 ("list_size", ctypes.c_int32), ("lds_bytes", ctypes.c_int32), ("fused_top", ctypes.c_int32),
                 ("frames_per_block", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class LdpcPlanProbe(ctypes.Structure):
+    """pl_ldpc_plan_probe: what the host-side planner decides for a flooding plan (no device call)."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("kernel", "threads", "lds_bytes", "use_global", "reg_variant", "grp",
+                                              "fpg", "tl", "npad", "compact", "ms36")] + \
+               [(f, ctypes.c_int64) for f in ("work_bytes_per_frame", "table_len", "grp_at", "ms_vw_at")] + \
+               [("digest", ctypes.c_uint64)]
+
+
+class LdpcLayeredPlanProbe(ctypes.Structure):
+    """pl_ldpc_layered_plan_probe: the layered kernel's geometry."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("kernel", "maxdc", "n_layers", "max_layer", "mw", "wave", "use_global",
+                                              "fpb", "threads", "lds_bytes")] + \
+               [(f, ctypes.c_int64) for f in ("state_bytes", "off_mm", "off_meta", "table_len")] + \
+               [("digest", ctypes.c_uint64)]
 
 
 def _load(path=LIB_PATH):
@@ -47,6 +64,9 @@ def _load(path=LIB_PATH):
     L.pl_polar_plan_create.argtypes = [I32, I32, P, I32, I32, PP]
     L.pl_ldpc_plan_create.argtypes = [I32, I32, P, P, I32, I32, I32, D, I32, PP]
     L.pl_ldpc_layered_plan_create.argtypes = [I32, I32, P, P, I32, P, P, I32, I32, D, I32, PP]
+    L.pl_debug_ldpc_plan_probe.argtypes = [I32, I32, P, P, I32, I32, I32, D, I32, I32, I32, ctypes.POINTER(LdpcPlanProbe)]
+    L.pl_debug_ldpc_layered_plan_probe.argtypes = [I32, I32, P, P, I32, P, P, I32, I32, D, I32, I32, I32,
+                                                   ctypes.POINTER(LdpcLayeredPlanProbe)]
     L.pl_ldpc_decode_soft.argtypes = [P, P, I64, I64, P, P, P, I64, P]
     L.pl_decode.argtypes = [P, P, I64, I64, P, P, P]
     L.pl_plan_reserve.argtypes = [P, I64, P]

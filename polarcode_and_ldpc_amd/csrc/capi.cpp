@@ -139,77 +139,6 @@ static int redo_metric(const pl_plan* p) {
     return p->pg.N <= (1 << PL_METRIC_FUSED_NMAX) ? pl::kRedoMetricFused : pl::kRedoMetricLean;
 }
 
-// ldpc_bp_grp_kernel's variable -> thread-slot map (slot q = 256 j + tid;
-// nslots >= n, -1 = empty).  The variable pass stores T'[tpos] (ds_write_b64:
-// lane groups of 16, bank pair tpos mod 16) and reads C'[tpos] (ds_read_b64:
-// lane groups of 32, element (tl + tpos) mod 32) for each of its DV edges; a
-// group's cost is, per edge k, the largest number of its lanes on one bank.
-// Greedy fill (each slot takes the unplaced variable that adds the fewest
-// same-bank lanes to its two groups), then hill climbing over slot swaps
-// (deterministic xorshift, sideways moves kept).  Any map gives the same
-// decoding; only the LDS conflicts change (MI355X_MICROARCH.md, LDS).
-static std::vector<int> ldpc_var_slots(int n, int dv, const std::vector<int32_t>& tp, int tl, int nslots) {
-    std::vector<int> vm(nslots, -1);
-    {
-        std::vector<char> used(n, 0);
-        std::vector<int> wcnt((size_t)dv * 16), rcnt((size_t)dv * 32);
-        const int empty = nslots - n;  // empty slots go to the end of the last groups
-        for (int q = 0; q < nslots - empty; ++q) {
-            if ((q & 15) == 0) std::fill(wcnt.begin(), wcnt.end(), 0);
-            if ((q & 31) == 0) std::fill(rcnt.begin(), rcnt.end(), 0);
-            int best = -1, bc = 1 << 30;
-            for (int v = 0; v < n; ++v) {
-                if (used[v]) continue;
-                int c = 0;
-                for (int k = 0; k < dv; ++k) {
-                    const int t = tp[(size_t)v * dv + k];
-                    c += wcnt[(size_t)k * 16 + t % 16] + rcnt[(size_t)k * 32 + (t + tl) % 32];
-                }
-                if (c < bc) { bc = c; best = v; if (c == 0) break; }
-            }
-            used[best] = 1;
-            vm[q] = best;
-            for (int k = 0; k < dv; ++k) {
-                const int t = tp[(size_t)best * dv + k];
-                ++wcnt[(size_t)k * 16 + t % 16];
-                ++rcnt[(size_t)k * 32 + (t + tl) % 32];
-            }
-        }
-    }
-    auto gcost = [&](int start, int size, int mod, int add) {
-        int c = 0;
-        for (int k = 0; k < dv; ++k) {
-            int cnt[32] = {0}, mx = 0;
-            for (int q = start; q < start + size; ++q) {
-                const int v = vm[q];
-                if (v < 0) continue;
-                const int b = (tp[(size_t)v * dv + k] + add) % mod;
-                mx = std::max(mx, ++cnt[b]);
-            }
-            c += mx;
-        }
-        return c;
-    };
-    auto groups_cost = [&](int a, int b) {
-        const int wa = a & ~15, wb = b & ~15, ra = a & ~31, rb = b & ~31;
-        int c = gcost(wa, 16, 16, 0) + gcost(ra, 32, 32, tl);
-        if (wb != wa) c += gcost(wb, 16, 16, 0);
-        if (rb != ra) c += gcost(rb, 32, 32, tl);
-        return c;
-    };
-    uint64_t x = 0x9E3779B97F4A7C15ull;
-    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
-    const int iters = 40 * nslots;
-    for (int it = 0; it < iters; ++it) {
-        const int a = (int)(rnd() % (uint64_t)nslots), b = (int)(rnd() % (uint64_t)nslots);
-        if (a == b || (vm[a] < 0 && vm[b] < 0)) continue;
-        const int before = groups_cost(a, b);
-        std::swap(vm[a], vm[b]);
-        if (groups_cost(a, b) > before) std::swap(vm[a], vm[b]);
-    }
-    return vm;
-}
-
 static int device_cus(int dev) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
@@ -360,253 +289,60 @@ extern "C" int pl_polar_plan_create(int32_t N, int32_t K, const uint8_t* frozen_
     return PL_OK;
 }
 
+// The LDPC planning switches (ldpc_plan.hpp; the planner itself reads no
+// environment).  The check kernel exists in the diagnostic build only; a
+// frames-per-workgroup request other than 1 means 2.
+static_assert(PL_LDPC_KERNEL_DEFAULT == pl::kLdpcKernelDefault && PL_LDPC_KERNEL_GENERIC == pl::kLdpcKernelGeneric &&
+              PL_LDPC_KERNEL_REG == pl::kLdpcKernelReg && PL_LDPC_KERNEL_COMPACT == pl::kLdpcKernelCompact &&
+              PL_LDPC_KERNEL_CHECK == pl::kLdpcKernelCheck, "include/polarldpc.h numbers the overrides as ldpc_plan.hpp");
+static pl::LdpcPlanOptions ldpc_options(int kernel, int bp_fpg, int lms_global) {
+    pl::LdpcPlanOptions o;
+    o.kernel = (kernel == pl::kLdpcKernelCheck && !PL_DIAG) ? pl::kLdpcKernelDefault : kernel;
+    o.bp_fpg = bp_fpg == 0 ? 0 : (bp_fpg == 1 ? 1 : 2);
+    o.lms_global = lms_global != 0;
+    return o;
+}
+// PL_LDPC_KERNEL, PL_BP_FPG and PL_LMS_GLOBAL: the one place that reads them
+static pl::LdpcPlanOptions ldpc_env_options() {
+    const char* lk = std::getenv("PL_LDPC_KERNEL");
+    const std::string k = lk ? lk : "";
+    const char* fpg = std::getenv("PL_BP_FPG");
+    return ldpc_options(k == "generic" ? pl::kLdpcKernelGeneric : k == "reg" ? pl::kLdpcKernelReg
+                        : k == "compact" ? pl::kLdpcKernelCompact : k == "check" ? pl::kLdpcKernelCheck
+                                                                                 : pl::kLdpcKernelDefault,
+                        (fpg && *fpg) ? (std::atoi(fpg) == 1 ? 1 : 2) : 0, env_int("PL_LMS_GLOBAL", 0));
+}
+
+// An LDPC plan object around the planner's tables, uploaded as one device buffer.
+static int ldpc_plan_upload(const std::vector<int32_t>& tables, pl_plan** p) {
+    *p = new pl_plan();
+    (*p)->kind = 1;
+    hipGetDevice(&(*p)->device);
+    (*p)->ldpc_chunk = std::max(1, env_int("PL_LDPC_CHUNK", 16384));
+    const hipError_t e = upload(&(*p)->d_ldpc, tables);
+    if (e == hipSuccess) return PL_OK;
+    pl_plan_destroy(*p);
+    return hipfail(e, "plan upload");
+}
+
 extern "C" int pl_ldpc_plan_create(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
                                    int32_t algo, int32_t max_iter, int32_t early_stop, double normalization,
                                    int32_t flags, pl_plan** out) {
     (void)flags;
     if (!out) return fail(PL_EINVAL, "out is NULL");
     *out = nullptr;
-    if (m < 0 || n < 1 || !row_ptr || (!col_idx && row_ptr[m] > 0)) return fail(PL_EINVAL, "bad H");
-    if (algo != PL_LDPC_BP && algo != PL_LDPC_MS) return fail(PL_EINVAL, "algo must be BP or MS");
-    if (max_iter < 1) return fail(PL_EINVAL, "max_iter must be >= 1");
-    const int E = row_ptr[m];
-    if (row_ptr[0] != 0 || E < 0) return fail(PL_EINVAL, "row_ptr[0] must be 0");
-    std::vector<int32_t> edge_chk(E), var_ptr(n + 1, 0), var_edge(E);
-    int maxdc = 0;
-    for (int c = 0; c < m; ++c) {
-        const int d = row_ptr[c + 1] - row_ptr[c];
-        if (d < 0) return fail(PL_EINVAL, "row_ptr not monotone");
-        if (d > maxdc) maxdc = d;
-        if (algo == PL_LDPC_MS && d == 1)
-            return fail(PL_EUNSUPPORTED, "min-sum on a degree-1 check (reference raises ValueError)");
-        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) {
-            if (col_idx[e] < 0 || col_idx[e] >= n) return fail(PL_EINVAL, "column index out of range");
-            if (e > row_ptr[c] && col_idx[e] <= col_idx[e - 1]) return fail(PL_EINVAL, "columns must ascend");
-            edge_chk[e] = c;
-            var_ptr[col_idx[e] + 1]++;
-        }
-    }
-    for (int v = 0; v < n; ++v) var_ptr[v + 1] += var_ptr[v];
-    int maxdv = 0;
-    for (int v = 0; v < n; ++v) maxdv = std::max(maxdv, var_ptr[v + 1] - var_ptr[v]);
-    if (maxdv > 128) return fail(PL_EUNSUPPORTED, "variable degree > 128");
-    // Device edge order: checks sorted by degree (stable), so the lanes of a
-    // wavefront run check loops of equal length; columns stay ascending within a
-    // check (the reference's product order).  No result depends on the check
-    // order: var_edge lists each variable's edges by ascending ORIGINAL check
-    // index, the order of the reference's np.sum over them (decoder.py:110-116).
-    std::vector<int32_t> order(m);
-    for (int c = 0; c < m; ++c) order[c] = c;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        return (row_ptr[a + 1] - row_ptr[a]) < (row_ptr[b + 1] - row_ptr[b]);
-    });
-    std::vector<int32_t> prow(m + 1, 0), pcol(E), new_edge(E);  // new_edge[original edge]
-    for (int k = 0; k < m; ++k) {
-        const int c = order[k];
-        prow[k + 1] = prow[k] + (row_ptr[c + 1] - row_ptr[c]);
-        for (int e = row_ptr[c], j = prow[k]; e < row_ptr[c + 1]; ++e, ++j) {
-            pcol[j] = col_idx[e];
-            new_edge[e] = j;
-            edge_chk[j] = k;
-        }
-    }
-    {
-        std::vector<int32_t> fill(var_ptr.begin(), var_ptr.end() - 1);
-        for (int c = 0; c < m; ++c)  // original check order
-            for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) var_edge[fill[col_idx[e]]++] = new_edge[e];
-    }
-    row_ptr = prow.data();
-    col_idx = pcol.data();
-    pl_plan* p = new pl_plan();
-    p->kind = 1;
-    hipGetDevice(&p->device);
-    pl::LdpcGeom& g = p->lg;
-    g.m = m; g.n = n; g.E = E; g.max_iter = max_iter; g.early_stop = early_stop ? 1 : 0; g.algo = algo;
-    g.maxdc = maxdc; g.maxdv = maxdv; g.norm = normalization;
-    g.regular = 1;
-    for (int c = 0; c < m && g.regular; ++c) g.regular = (row_ptr[c + 1] - row_ptr[c]) == maxdc;
-    for (int v = 0; v < n && g.regular; ++v) g.regular = (var_ptr[v + 1] - var_ptr[v]) == maxdv;
-    g.threads = E <= 4096 ? 256 : 1024;
-    if (E >= (1 << 20) || maxdc >= (1 << 11)) { delete p; return fail(PL_EUNSUPPORTED, "code too large"); }
-    const size_t lds_small = (size_t)8 * m + n;                 // syndrome [2][m] u32 + decisions [n]
-    const size_t lds_all = (size_t)2 * (size_t)E * 8 + lds_small;  // + T[E], C[E]
-    g.use_global = lds_all > 64 * 1024 ? 1 : 0;
-    g.lds_bytes = (int)(((g.use_global ? lds_small : lds_all) + 15) & ~(size_t)15);
-    // check-per-thread kernel (ldpc.hip ldpc_check_kernel): diagnostic build only, PL_LDPC_KERNEL=check
-    const char* lk = std::getenv("PL_LDPC_KERNEL");
-    g.check_kernel = PL_DIAG && !g.use_global && lk && std::string(lk) == "check" ? 1 : 0;
-    // register-cached kernel: constant variable degree < 8, LDS-resident state
-    g.reg_variant = 0;
-    if (!g.use_global && !g.check_kernel && !(lk && std::string(lk) == "generic")) {
-        bool regular = true;
-        for (int v = 0; v < n && regular; ++v) regular = (var_ptr[v + 1] - var_ptr[v]) == maxdv;
-        if (regular && maxdv < 8 && E < 65536) g.reg_variant = pl::ldpc_reg_variant(maxdv, E, n);
-        if (g.reg_variant) {
-            g.threads = 256;
-            // + the per-wavefront BP tanh lists (ldpc_reg_kernel)
-            const size_t base = ((size_t)2 * E * 8 + lds_small + 15) & ~(size_t)15;
-            g.lds_bytes = (int)((base + pl::ldpc_reg_list_bytes(g.reg_variant) + 15) & ~(size_t)15) + 128;  // + vote words
-        }
-    }
-    // BP on a reg variant: degree-grouped check products (ldpc_bp_grp_kernel).
-    // Slot s holds edges 64 s .. 64 s + 63 (degree-sorted, check-major); D_s =
-    // the largest check degree among them; check c's inputs sit at T' offset
-    // off[c] (even), padded with 1.0 to the largest D_s of the slots holding its
-    // edges.  PL_LDPC_KERNEL=reg keeps ldpc_reg_kernel's per-lane products.
-    std::vector<int32_t> grp_meta, var_tpos;
-    g.grp = 0;
-    g.tl = 0;
-    if (g.reg_variant && algo == PL_LDPC_BP && maxdc <= 15 && !(lk && std::string(lk) == "reg")) {
-        const int slots = 4 * pl::ldpc_reg_ept(g.reg_variant);
-        std::vector<int> dslot(slots, 0), dpad(m, 0), off(m + 1, 0);
-        for (int e = 0; e < E; ++e) {
-            const int c = edge_chk[e], d = row_ptr[c + 1] - row_ptr[c];
-            dslot[e / 64] = std::max(dslot[e / 64], d);
-        }
-        for (int e = 0; e < E; ++e) dpad[edge_chk[e]] = std::max(dpad[edge_chk[e]], dslot[e / 64]);
-        for (int c = 0; c < m; ++c) off[c + 1] = off[c] + ((dpad[c] + 1) & ~1);
-        // T', C' positions [0, off[m]) hold the checks, [off[m], off[m] + 16) is a sink
-        // for the lanes of a slot past the last edge (they read it and store into it)
-        const int sink = off[m], tl = off[m] + 16;
-        const size_t base = ((size_t)16 * tl + (size_t)4 * ((m + 3) & ~3) + 15) & ~(size_t)15;  // T', C', syndrome
-        const size_t lds = (base + pl::ldpc_reg_list_bytes(g.reg_variant) + 15) & ~(size_t)15;
-        if (tl < 65536 && lds <= 64 * 1024) {
-            g.grp = 1;
-            // two frames per workgroup, one after the other (ldpc_bp_grp_kernel FPG):
-            // valid codewords (early stop) 0.777 -> 0.742 ms per 65 536 frames, the
-            // harness frames (20 iterations) equal; PL_BP_FPG=1 restores one.  Only
-            // the (DV, EPT, VPT) = (3, 6, 2) instance: the larger ones' two-frame
-            // builds spill 24-41 more VGPRs than their one-frame builds
-            const bool fpg2 = maxdv == 3 && pl::ldpc_reg_ept(g.reg_variant) == 6;
-            g.fpg = env_int("PL_BP_FPG", fpg2 ? 2 : 1) == 1 ? 1 : 2;
-            g.tl = tl;
-            g.lds_bytes = (int)lds;
-            // sorted slot s goes to the thread slot (j = s / 4, wavefront w) in snake
-            // order (w = s % 4 for even j, 3 - s % 4 for odd j), so the four
-            // wavefronts -- one per SIMD -- get products of about equal total length
-            grp_meta.assign((size_t)slots * 64, 0);
-            for (int s = 0; s < slots; ++s) {
-                const int j = s / 4, w = (j & 1) ? 3 - (s & 3) : (s & 3);
-                for (int l = 0; l < 64; ++l) {
-                    const int e = 64 * s + l, q = 256 * j + 64 * w + l;
-                    if (e < E) {
-                        const int c = edge_chk[e];
-                        grp_meta[q] = off[c] | ((e - row_ptr[c]) << 16) | (dslot[s] << 20);
-                    } else {  // reads and stores the sink (position 15 skips no factor)
-                        grp_meta[q] = sink | (15 << 16) | (dslot[s] << 20);
-                    }
-                }
-            }
-            // variables in thread-slot order (slot q = 256 j + tid): T' position and
-            // check of each edge, variable index (-1: empty); the order chosen so
-            // the variable pass's scattered LDS accesses conflict little
-            std::vector<int32_t> tp((size_t)n * maxdv), vck((size_t)n * maxdv);
-            for (int v = 0; v < n; ++v)
-                for (int k = 0; k < maxdv; ++k) {
-                    const int e = var_edge[var_ptr[v] + k], c = edge_chk[e];
-                    tp[(size_t)v * maxdv + k] = off[c] + (e - row_ptr[c]);
-                    vck[(size_t)v * maxdv + k] = c;
-                }
-            const int nslots = 256 * pl::ldpc_reg_vpt(g.reg_variant);
-            const std::vector<int> vmap = ldpc_var_slots(n, maxdv, tp, tl, nslots);
-            // + the pad positions (T' = 1.0 from the first write on), -1 filled to 256
-            std::vector<char> real(sink, 0);
-            for (int e = 0; e < E; ++e) real[off[edge_chk[e]] + (e - row_ptr[edge_chk[e]])] = 1;
-            std::vector<int32_t> pads;
-            for (int q = 0; q < sink; ++q)
-                if (!real[q]) pads.push_back(q);
-            g.npad = (int)((pads.size() + 255) / 256 * 256);
-            pads.resize(g.npad, -1);
-            var_tpos.assign((size_t)nslots * (2 * maxdv + 1), 0);
-            for (int q = 0; q < nslots; ++q) {
-                const int v = vmap[q];
-                var_tpos[(size_t)2 * maxdv * nslots + q] = v;
-                for (int k = 0; k < maxdv; ++k) {
-                    var_tpos[(size_t)q * maxdv + k] = v >= 0 ? tp[(size_t)v * maxdv + k] : 0;
-                    var_tpos[(size_t)maxdv * nslots + (size_t)q * maxdv + k] = v >= 0 ? vck[(size_t)v * maxdv + k] : 0;
-                }
-            }
-            var_tpos.insert(var_tpos.end(), pads.begin(), pads.end());
-        }
-    }
-    // min-sum codes whose T/C arrays exceed LDS: compressed check state in LDS
-    g.compact = 0;
-    if (g.use_global && algo == 1 && maxdc <= 15 && !(lk && std::string(lk) == "generic")) {
-        const size_t lds_c = (((((size_t)8 * n + 15) & ~(size_t)15) + (size_t)20 * m + 15) & ~(size_t)15) + 128;  // + vote words
-        if (lds_c <= 160 * 1024) {
-            g.compact = 1;
-            g.use_global = 0;
-            g.threads = 1024;
-            g.lds_bytes = (int)((lds_c + 15) & ~(size_t)15);
-        }
-    }
-    // (3,6)-regular min-sum of n = 2048 / 4096 / 8192 (the BASELINE n = 8192 code):
-    // ldpc_ms36_kernel (PL_LDPC_KERNEL=compact keeps ldpc_ms_compact_kernel)
-    g.ms36 = 0;
-    std::vector<int32_t> ms_vw;
-    if (g.compact && g.regular && maxdv == 3 && maxdc == 6 && 2 * m == n && pl::ldpc_ms36_lds(n) > 0 &&
-        !(lk && std::string(lk) == "compact")) {
-        g.ms36 = n / 1024;
-        g.lds_bytes = pl::ldpc_ms36_lds(n);
-        const uint32_t REC = 8u * (uint32_t)n, MET = 16u * (uint32_t)n;  // ldpc_ms36_kernel's LDS layout
-        // [n][8]: per variable its three edge words and meta addresses; then
-        // [m][4]: per check the LDS byte addresses 8v of its six variables, two per word
-        ms_vw.assign((size_t)n * 8 + (size_t)m * 4, 0);
-        for (int v = 0; v < n; ++v)
-            for (int k = 0; k < 3; ++k) {
-                const int e = var_edge[var_ptr[v] + k], c = edge_chk[e], pos = e - row_ptr[c];
-                ms_vw[(size_t)v * 8 + k] = (int32_t)((REC + 16u * (uint32_t)c) | (3u * (uint32_t)pos));
-                ms_vw[(size_t)v * 8 + 3 + k] = (int32_t)(MET + 4u * (uint32_t)c);
-            }
-        for (int c = 0; c < m; ++c)
-            for (int k = 0; k < 3; ++k)
-                ms_vw[(size_t)n * 8 + (size_t)c * 4 + k] =
-                    (int32_t)((8u * (uint32_t)col_idx[row_ptr[c] + 2 * k]) | ((8u * (uint32_t)col_idx[row_ptr[c] + 2 * k + 1]) << 16));
-    }
-    if (g.check_kernel) {
-        g.threads = 256;
-        g.lds_bytes = (int)(((size_t)(2 * (size_t)E + n) * 8 + 15) & ~(size_t)15);
-    }
-    std::vector<int32_t> all;
-    all.insert(all.end(), row_ptr, row_ptr + m + 1);
-    all.insert(all.end(), col_idx, col_idx + E);
-    all.insert(all.end(), edge_chk.begin(), edge_chk.end());
-    all.insert(all.end(), var_ptr.begin(), var_ptr.end());
-    all.insert(all.end(), var_edge.begin(), var_edge.end());
-    std::vector<int32_t> edge_meta(E), var_chk(E);
-    for (int k = 0; k < m; ++k)
-        for (int e = row_ptr[k]; e < row_ptr[k + 1]; ++e) edge_meta[e] = row_ptr[k] | ((row_ptr[k + 1] - row_ptr[k]) << 20);
-    for (int k = 0; k < E; ++k) var_chk[k] = edge_chk[var_edge[k]];
-    std::vector<int32_t> var_cp(E);
-    for (int k = 0; k < E; ++k) {
-        const int e = var_edge[k], c = edge_chk[e];
-        var_cp[k] = (c << 4) | ((e - row_ptr[c]) & 15);
-    }
-    all.insert(all.end(), edge_meta.begin(), edge_meta.end());
-    all.insert(all.end(), var_chk.begin(), var_chk.end());
-    all.insert(all.end(), var_cp.begin(), var_cp.end());
-    const size_t grp_at = all.size();
-    all.insert(all.end(), grp_meta.begin(), grp_meta.end());
-    all.insert(all.end(), var_tpos.begin(), var_tpos.end());
-    all.resize((all.size() + 3) & ~(size_t)3, 0);  // ms_vw: 16-byte aligned (uint4 loads)
-    const size_t vw_at = all.size();
-    all.insert(all.end(), ms_vw.begin(), ms_vw.end());
-    hipError_t e = upload(&p->d_ldpc, all);
-    if (e != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "plan upload"); }
-    p->ld.row_ptr = p->d_ldpc;
-    p->ld.col_idx = p->ld.row_ptr + (m + 1);
-    p->ld.edge_chk = p->ld.col_idx + E;
-    p->ld.var_ptr = p->ld.edge_chk + E;
-    p->ld.var_edge = p->ld.var_ptr + (n + 1);
-    p->ld.edge_meta = p->ld.var_edge + E;
-    p->ld.var_chk = p->ld.edge_meta + E;
-    p->ld.var_cp = p->ld.var_chk + E;
-    p->ld.grp_meta = g.grp ? p->d_ldpc + grp_at : nullptr;
-    p->ld.var_tpos = g.grp ? p->d_ldpc + grp_at + grp_meta.size() : nullptr;
-    p->ld.ms_vw = g.ms36 ? reinterpret_cast<const uint32_t*>(p->d_ldpc + vw_at) : nullptr;
-    if ((e = pl::ldpc_prepare(g)) != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "hipFuncSetAttribute"); }
-    p->ws_unit = pl::ldpc_work_bytes_per_frame(g);
-    p->ldpc_chunk = std::max(1, env_int("PL_LDPC_CHUNK", 16384));
+    // every argument check (ldpc_plan.cpp) comes before the first device call
+    pl::LdpcHostPlan hp;
+    const pl::PlanStatus st =
+        pl::ldpc_plan_build(m, n, row_ptr, col_idx, algo, max_iter, early_stop, normalization, ldpc_env_options(), &hp);
+    if (st.code) return fail(st.code, st.msg);
+    pl_plan* p;
+    if (int rc = ldpc_plan_upload(hp.tables, &p)) return rc;
+    p->lg = hp.geom;
+    p->ld = hp.dev(p->d_ldpc);
+    const hipError_t e = pl::ldpc_prepare(p->lg);
+    if (e != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "hipFuncSetAttribute"); }
+    p->ws_unit = pl::ldpc_work_bytes_per_frame(p->lg);
     *out = p;
     return PL_OK;
 }
@@ -618,76 +354,58 @@ extern "C" int pl_ldpc_layered_plan_create(int32_t m, int32_t n, const int32_t* 
     (void)flags;
     if (!out) return fail(PL_EINVAL, "out is NULL");
     *out = nullptr;
-    // every argument check comes before the first device call
-    if (m < 0 || n < 1 || !row_ptr || (!col_idx && row_ptr[m] > 0)) return fail(PL_EINVAL, "bad H");
-    if (max_iter < 0) return fail(PL_EINVAL, "max_iter must be >= 0");
-    const int E = row_ptr[m];
-    if (row_ptr[0] != 0 || E < 0) return fail(PL_EINVAL, "row_ptr[0] must be 0");
-    // row_ptr monotone and within [0, E] before any col_idx entry is read
-    for (int c = 0; c < m; ++c)
-        if (row_ptr[c + 1] < row_ptr[c] || row_ptr[c + 1] > E) return fail(PL_EINVAL, "row_ptr not monotone");
-    int maxdc = 0;
-    bool deg1 = false;
-    for (int c = 0; c < m; ++c) {
-        const int d = row_ptr[c + 1] - row_ptr[c];
-        maxdc = std::max(maxdc, d);
-        deg1 |= d == 1;
-        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) {
-            if (col_idx[e] < 0 || col_idx[e] >= n) return fail(PL_EINVAL, "column index out of range");
-            if (e > row_ptr[c] && col_idx[e] <= col_idx[e - 1]) return fail(PL_EINVAL, "columns must ascend");
-        }
-    }
-    if (n_layers < 0 || !layer_ptr || (m > 0 && !layer_rows) || layer_ptr[0] != 0 || layer_ptr[n_layers] != m)
-        return fail(PL_EINVAL, "layers must list every row exactly once");
-    int max_layer = 0;
-    {
-        std::vector<uint8_t> seen((size_t)m, 0);
-        std::vector<int32_t> mark((size_t)n, -1);  // last layer that touched the column
-        for (int l = 0; l < n_layers; ++l) {
-            if (layer_ptr[l + 1] < layer_ptr[l] || layer_ptr[l + 1] > m)
-                return fail(PL_EINVAL, "layer_ptr not monotone");
-            max_layer = std::max(max_layer, layer_ptr[l + 1] - layer_ptr[l]);
-            for (int k = layer_ptr[l]; k < layer_ptr[l + 1]; ++k) {
-                const int c = layer_rows[k];
-                if (c < 0 || c >= m) return fail(PL_EINVAL, "layer row index out of range");
-                if (seen[c]) return fail(PL_EINVAL, "layers must list every row exactly once (row " + std::to_string(c) + " repeats)");
-                seen[c] = 1;
-                for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) {
-                    if (mark[col_idx[e]] == l)
-                        return fail(PL_EINVAL, "two rows of layer " + std::to_string(l) + " share column " +
-                                                   std::to_string(col_idx[e]));
-                    mark[col_idx[e]] = l;
-                }
-            }
-        }
-        // layer_ptr[n_layers] == m entries, none repeated, all in range: every row is listed
-    }
-    // max_iter == 0 evaluates no check (MSDecoder raises only once an iteration runs)
-    if (deg1 && max_iter > 0) return fail(PL_EUNSUPPORTED, "min-sum on a degree-1 check (reference raises ValueError)");
-    if (maxdc >= (1 << 11)) return fail(PL_EUNSUPPORTED, "check degree >= 2048");
-    pl_plan* p = new pl_plan();
-    p->kind = 1;
+    // every argument check (ldpc_plan.cpp) comes before the first device call
+    pl::LmsHostPlan hp;
+    const pl::PlanStatus st = pl::lms_plan_build(m, n, row_ptr, col_idx, n_layers, layer_ptr, layer_rows, max_iter,
+                                                 early_stop, normalization, ldpc_env_options(), &hp);
+    if (st.code) return fail(st.code, st.msg);
+    pl_plan* p;
+    if (int rc = ldpc_plan_upload(hp.tables, &p)) return rc;
     p->layered = true;
-    hipGetDevice(&p->device);
-    p->lg.n = n; p->lg.m = m; p->lg.E = E;
-    pl::LmsGeom& g = p->lms;
-    g.m = m; g.n = n; g.E = E; g.max_iter = max_iter; g.early_stop = early_stop ? 1 : 0; g.maxdc = maxdc;
-    g.n_layers = n_layers; g.max_layer = max_layer; g.norm = normalization;
-    pl::lms_geom(&g, env_int("PL_LMS_GLOBAL", 0) != 0);
-    std::vector<int32_t> all(row_ptr, row_ptr + m + 1);
-    all.insert(all.end(), col_idx, col_idx + E);
-    all.insert(all.end(), layer_ptr, layer_ptr + n_layers + 1);
-    all.insert(all.end(), layer_rows, layer_rows + m);
-    hipError_t e = upload(&p->d_ldpc, all);
-    if (e != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "plan upload"); }
-    p->lmsd.row_ptr = p->d_ldpc;
-    p->lmsd.col_idx = p->lmsd.row_ptr + (m + 1);
-    p->lmsd.layer_ptr = p->lmsd.col_idx + E;
-    p->lmsd.layer_rows = p->lmsd.layer_ptr + (n_layers + 1);
-    if ((e = pl::lms_prepare(g)) != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "hipFuncSetAttribute"); }
-    p->ws_unit = g.use_global ? (size_t)g.state_bytes : 0;
-    p->ldpc_chunk = std::max(1, env_int("PL_LDPC_CHUNK", 16384));
+    p->lg.n = n; p->lg.m = m; p->lg.E = hp.geom.E;
+    p->lms = hp.geom;
+    p->lmsd = hp.dev(p->d_ldpc);
+    const hipError_t e = pl::lms_prepare(p->lms);
+    if (e != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "hipFuncSetAttribute"); }
+    p->ws_unit = p->lms.use_global ? (size_t)p->lms.state_bytes : 0;
     *out = p;
+    return PL_OK;
+}
+
+// The planner's decisions for a code, with no plan object and no device call.
+extern "C" int pl_debug_ldpc_plan_probe(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                                        int32_t algo, int32_t max_iter, int32_t early_stop, double normalization,
+                                        int32_t kernel_override, int32_t bp_fpg, int32_t lms_global,
+                                        pl_ldpc_plan_probe* out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    if (kernel_override < 0 || kernel_override > PL_LDPC_KERNEL_CHECK) return fail(PL_EINVAL, "bad kernel_override");
+    pl::LdpcHostPlan hp;
+    const pl::PlanStatus st = pl::ldpc_plan_build(m, n, row_ptr, col_idx, algo, max_iter, early_stop, normalization,
+                                                  ldpc_options(kernel_override, bp_fpg, lms_global), &hp);
+    if (st.code) return fail(st.code, st.msg);
+    const pl::LdpcGeom& g = hp.geom;
+    *out = pl_ldpc_plan_probe{pl::ldpc_kernel_code(g), g.threads, g.lds_bytes, g.use_global, g.reg_variant, g.grp,
+                              g.fpg, g.tl, g.npad, g.compact, g.ms36, (int64_t)pl::ldpc_work_bytes_per_frame(g),
+                              (int64_t)hp.tables.size(), (int64_t)hp.at.grp_meta, (int64_t)hp.at.ms_vw,
+                              pl::plan_tables_digest(hp.tables)};
+    return PL_OK;
+}
+
+extern "C" int pl_debug_ldpc_layered_plan_probe(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
+                                                int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_rows,
+                                                int32_t max_iter, int32_t early_stop, double normalization,
+                                                int32_t kernel_override, int32_t bp_fpg, int32_t lms_global,
+                                                pl_ldpc_layered_plan_probe* out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    pl::LmsHostPlan hp;
+    const pl::PlanStatus st = pl::lms_plan_build(m, n, row_ptr, col_idx, n_layers, layer_ptr, layer_rows, max_iter,
+                                                 early_stop, normalization,
+                                                 ldpc_options(kernel_override, bp_fpg, lms_global), &hp);
+    if (st.code) return fail(st.code, st.msg);
+    const pl::LmsGeom& g = hp.geom;
+    *out = pl_ldpc_layered_plan_probe{pl::lms_kernel_code(g), g.maxdc, g.n_layers, g.max_layer, g.mw, g.wave,
+                                      g.use_global, g.fpb, g.threads, g.lds_bytes, g.state_bytes, g.off_mm, g.off_meta,
+                                      (int64_t)hp.tables.size(), pl::plan_tables_digest(hp.tables)};
     return PL_OK;
 }
 
@@ -1160,14 +878,14 @@ extern "C" int pl_plan_get_info(const pl_plan* p, pl_plan_info* info) {
     } else if (p->layered) {
         info->kind = 1; info->n_in = p->lms.n; info->n_out = p->lms.n; info->list_size = 0;
         info->lds_bytes = p->lms.lds_bytes; info->fused_top = 0; info->frames_per_block = p->lms.fpb;
-        info->reserved = p->lms.use_global ? 10 : 9;  // layered min-sum: 9 state in LDS, 10 in the workspace
+        info->reserved = pl::lms_kernel_code(p->lms);  // layered min-sum: 9 state in LDS, 10 in the workspace
     } else {
         info->kind = 1; info->n_in = p->lg.n; info->n_out = p->lg.n; info->list_size = 0;
         info->lds_bytes = p->lg.lds_bytes; info->fused_top = 0; info->frames_per_block = p->lg.fpg > 1 ? p->lg.fpg : 1;
         // kernel: 2 register-cached, 7 register-cached BP with degree-grouped products,
         // 1 generic (LDS or global workspace), 3 thread-per-check, 5 min-sum with compressed check state,
         // 8 (3,6)-regular min-sum with rebuild-ready check state
-        info->reserved = p->lg.ms36 ? 8 : p->lg.compact ? 5 : (p->lg.check_kernel ? 3 : (p->lg.grp ? 7 : (p->lg.reg_variant ? 2 : 1)));
+        info->reserved = pl::ldpc_kernel_code(p->lg);
     }
     return PL_OK;
 }

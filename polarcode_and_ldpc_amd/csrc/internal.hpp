@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ldpc_plan.hpp"
+
 #ifndef PL_METRIC_FUSED_NMAX
 // polar tree instances with n <= this use the fused log1p(exp(-x))
 // (log1p_exp_neg): N=1024 L=8 -1.9 %, L=32 -2.6 % (round 4); N=4096 L=8 +3.6 %
@@ -117,44 +119,7 @@ hipError_t crc_append_launch(uint8_t* msg, int64_t ld, int64_t batch, int k_data
 hipError_t count_errors_launch(const uint8_t* ref, int64_t ldr, const uint8_t* dec, int64_t ldd,
                                int width, int64_t batch, int64_t* counts, hipStream_t s);
 
-// ---- LDPC ----
-struct LdpcGeom {
-    int m, n, E, max_iter, early_stop, algo, maxdc, maxdv;
-    double norm;
-    int threads;       // threads per workgroup (one frame per workgroup)
-    int lds_bytes;     // 0 => messages live in the global workspace
-    int use_global;
-    int check_kernel;  // 1: ldpc_check_kernel (thread per check, state in LDS)
-    int reg_variant;   // > 0: ldpc_reg_kernel instance (constant variable degree, LDS state)
-    int compact;       // 1: ldpc_ms_compact_kernel (min-sum, compressed check state in LDS)
-    int regular;       // every check has degree maxdc and every variable degree maxdv
-    int grp;           // BP reg variant: ldpc_bp_grp_kernel (degree-grouped products, padded T'/C')
-    int tl;            // grp: length of the padded T'/C' arrays (doubles)
-    int npad;          // grp: pad positions listed after the variable slots (a multiple of 256, -1 filled)
-    int ms36;          // > 0: ldpc_ms36_kernel<ms36> ((3,6)-regular min-sum, n = 1024 ms36)
-    int fpg;           // grp: frames per workgroup (1 or 2)
-};
-struct LdpcDev {
-    const int32_t* row_ptr;   // [m+1]
-    const int32_t* col_idx;   // [E]   (check-major edge -> variable)
-    const int32_t* edge_chk;  // [E]   edge -> check
-    const int32_t* var_ptr;   // [n+1]
-    const int32_t* var_edge;  // [E]   var-major list of check-major edge ids (ascending check)
-    const int32_t* edge_meta; // [E]   first edge of the edge's check | check degree << 20
-    const int32_t* var_chk;   // [E]   check of var_edge[k]
-    const int32_t* var_cp;    // [E]   check << 4 | position in the check, of var_edge[k]
-    // grp (ldpc_bp_grp_kernel): per edge slot (256 EPT of them) the T' position
-    // of the edge's check | position in the check << 16 | its slot's D_s << 20;
-    // per variable slot q (256 VPT of them): [q][DV] T' positions, [q][DV]
-    // checks, then [q] the variable (-1: none); then npad pad positions
-    const int32_t* grp_meta;  // [256 EPT]
-    const int32_t* var_tpos;  // [256 VPT (2 DV + 1)]
-    // ms36 (ldpc_ms36_kernel), 16-byte aligned: per variable [8] u32, its three
-    // edge words (LDS rec address of the check | 3 * position) then the three
-    // LDS meta addresses, in the reference's np.sum order (ascending check);
-    // then per check [4] u32, the LDS addresses 8v of its six variables, two per word
-    const uint32_t* ms_vw;    // [n][8] + [m][4]
-};
+// ---- LDPC (ldpc.hip); LdpcGeom / LdpcDev and the planner that fills them: ldpc_plan.hpp ----
 hipError_t ldpc_launch(const LdpcGeom& g, const LdpcDev& d, const double* llr, int64_t ld,
                        uint8_t* bits, int32_t* iters, int64_t batch, double* work, hipStream_t s);
 hipError_t ldpc_prepare(const LdpcGeom& g);
@@ -162,33 +127,8 @@ hipError_t ldpc_prepare(const LdpcGeom& g);
 hipError_t ldpc_launch_stamped(const LdpcGeom& g, const LdpcDev& d, const double* llr, int64_t ld, uint8_t* bits,
                                int32_t* iters, int64_t batch, unsigned long long* stamps, hipStream_t s);
 #endif
-size_t ldpc_work_bytes_per_frame(const LdpcGeom& g);
-int ldpc_reg_variant(int dv, int E, int n);  // 0: none fits
-size_t ldpc_reg_list_bytes(int variant);      // BP tanh lists of an ldpc_reg_kernel instance
-int ldpc_reg_ept(int variant);                // edges per thread of an ldpc_reg_kernel instance
-int ldpc_reg_vpt(int variant);                // variables per thread
-int ldpc_ms36_lds(int n);                     // LDS of the ldpc_ms36_kernel instance for n (0: none)
 
-// ---- layered min-sum (ldpc_layered.hip) ----
-struct LmsGeom {
-    int m, n, E, max_iter, early_stop, maxdc;
-    int n_layers, max_layer;  // layers and the checks of the largest one
-    double norm;
-    int mw;                   // meta words per check (1: every degree <= 16)
-    int wave;                 // 1: one wavefront per frame (max_layer <= 64); 0: one workgroup per frame
-    int use_global;           // state in the workspace instead of LDS
-    int fpb;                  // frames per workgroup
-    int threads, lds_bytes;
-    int64_t state_bytes;      // per frame: P[n] f64, then at off_mm [m] double2, at off_meta [m][mw] u32
-    int64_t off_mm, off_meta;
-};
-struct LmsDev {
-    const int32_t* row_ptr;     // [m+1]  H as given (original row order)
-    const int32_t* col_idx;     // [E]
-    const int32_t* layer_ptr;   // [n_layers+1]
-    const int32_t* layer_rows;  // [m]    rows layer by layer
-};
-void lms_geom(LmsGeom* g, bool force_global);
+// ---- layered min-sum (ldpc_layered.hip); LmsGeom / LmsDev: ldpc_plan.hpp ----
 hipError_t lms_prepare(const LmsGeom& g);
 // post: fp64 [batch][ld_post] posteriors or null; work: [batch] state slices (use_global) or null
 hipError_t lms_launch(const LmsGeom& g, const LmsDev& d, const double* llr, int64_t ld, uint8_t* bits, int32_t* iters,

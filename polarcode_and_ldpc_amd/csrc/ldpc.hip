@@ -184,7 +184,7 @@ ldpc_decode_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, int64
         lds += (size_t)2 * E * sizeof(double);
     }
     double* C = T + E;
-    uint32_t* syn = reinterpret_cast<uint32_t*>(lds);  // [2][m]
+    uint32_t* syn = reinterpret_cast<uint32_t*>(lds);  // [2][m]  (sized by ldpc_generic_lds / ldpc_small_lds, ldpc_plan.hpp)
     uint8_t* bt = lds + (size_t)8 * m;                  // [n]
     const double* __restrict__ ch = llr + frame * ld;
     auto tin = [&](double x) -> double {
@@ -310,7 +310,7 @@ ldpc_reg_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, int64_t 
     // BP: per-wavefront lists of the edges whose v2c needs a tanh (|x| <= 14.52
     // or NaN), 16-bit edge indices (E < 65536), 64*VPT*DV per wavefront: each
     // wavefront compacts and evaluates its own, so the tanh pass needs no
-    // workgroup barrier (capi.cpp sizes it with ldpc_reg_list_bytes)
+    // workgroup barrier (LDS layout and size: ldpc_reg_lds, ldpc_plan.hpp)
     uint16_t* work = reinterpret_cast<uint16_t*>(smem + (((size_t)16 * E + (size_t)8 * m + n + 15) & ~(size_t)15));
     uint32_t* vote = reinterpret_cast<uint32_t*>(smem + g.lds_bytes - 128);  // [2][16] (wg_any)
     const double* __restrict__ ch = llr + frame * ld;
@@ -542,7 +542,7 @@ ldpc_bp_grp_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, int64
     // whose decision flips toggles its checks' parities (no per-iteration reset,
     // and the LDS atomics only where a decision changed)
     const int mp = (m + 3) & ~3;
-    uint32_t* syn = reinterpret_cast<uint32_t*>(smem + (size_t)16 * tl);  // [mp]
+    uint32_t* syn = reinterpret_cast<uint32_t*>(smem + (size_t)16 * tl);  // [mp]  (sized by ldpc_grp_lds, ldpc_plan.hpp)
     uint16_t* work = reinterpret_cast<uint16_t*>(smem + (((size_t)16 * tl + (size_t)4 * mp + 15) & ~(size_t)15));
     const int lane = __lane_id();
 
@@ -724,43 +724,19 @@ ldpc_bp_grp_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, int64
 #undef PL_GSTAMP
 }
 
-// (DV, EPT, VPT) instances of ldpc_reg_kernel: E <= 256*EPT, n <= 256*VPT
-struct RegVariant { int dv, ept, vpt; void* k[4]; };  // BP, MS, BP degree-grouped (1, 2 frames per group)
-template <int DV, int EPT, int VPT>
-static RegVariant reg_variant() {
-    return {DV, EPT, VPT,
-            {(void*)ldpc_reg_kernel<0, DV, EPT, VPT>, (void*)ldpc_reg_kernel<1, DV, EPT, VPT>,
+// The kernels of the (DV, EPT, VPT) instances kLdpcRegVariants (ldpc_plan.hpp),
+// indexed as that array: BP, MS, BP degree-grouped (1, 2 frames per group)
+struct RegKernels { void* k[4]; };
+template <int I>
+static RegKernels reg_kernels() {
+    constexpr int DV = kLdpcRegVariants[I].dv, EPT = kLdpcRegVariants[I].ept, VPT = kLdpcRegVariants[I].vpt;
+    return {{(void*)ldpc_reg_kernel<0, DV, EPT, VPT>, (void*)ldpc_reg_kernel<1, DV, EPT, VPT>,
              (void*)ldpc_bp_grp_kernel<DV, EPT, VPT>, (void*)ldpc_bp_grp_kernel<DV, EPT, VPT, false, 2>}};
 }
-static const RegVariant* reg_table(int& count) {
-    // E = DV n for a constant variable degree, so (3, 8, 2) and (3, 16, 4) could
-    // never be picked ahead of (3, 6, 2) / (3, 12, 4): not built
-    static const RegVariant t[] = {reg_variant<3, 6, 2>(), reg_variant<3, 12, 4>(), reg_variant<4, 8, 2>(),
-                                   reg_variant<4, 16, 4>()};
-    count = (int)(sizeof(t) / sizeof(t[0]));
-    return t;
-}
-size_t ldpc_reg_list_bytes(int variant) {
-    int cnt;
-    const RegVariant* t = reg_table(cnt);
-    return variant > 0 && variant <= cnt ? (size_t)256 * t[variant - 1].vpt * t[variant - 1].dv * 2 : 0;
-}
-int ldpc_reg_vpt(int variant) {
-    int cnt;
-    const RegVariant* t = reg_table(cnt);
-    return variant > 0 && variant <= cnt ? t[variant - 1].vpt : 0;
-}
-int ldpc_reg_ept(int variant) {
-    int cnt;
-    const RegVariant* t = reg_table(cnt);
-    return variant > 0 && variant <= cnt ? t[variant - 1].ept : 0;
-}
-int ldpc_reg_variant(int dv, int E, int n) {
-    int cnt;
-    const RegVariant* t = reg_table(cnt);
-    for (int i = 0; i < cnt; ++i)
-        if (t[i].dv == dv && E <= 256 * t[i].ept && n <= 256 * t[i].vpt) return i + 1;
-    return 0;
+static const RegKernels& reg_kernels_of(int variant) {
+    static_assert(kLdpcRegVariantCount == 4, "one reg_kernels<I>() per entry of kLdpcRegVariants");
+    static const RegKernels t[] = {reg_kernels<0>(), reg_kernels<1>(), reg_kernels<2>(), reg_kernels<3>()};
+    return t[variant - 1];
 }
 
 // ---- min-sum with compressed check state (codes whose T/C arrays exceed LDS)
@@ -908,7 +884,7 @@ ldpc_ms_compact_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, i
     if (frame >= batch) return;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = g.n, m = g.m;
-    double* tot = reinterpret_cast<double*>(smem);
+    double* tot = reinterpret_cast<double*>(smem);  // layout sized by ldpc_compact_lds (ldpc_plan.hpp)
     double2* smin = reinterpret_cast<double2*>(smem + (((size_t)8 * n + 15) & ~(size_t)15));
     uint32_t* smeta = reinterpret_cast<uint32_t*>(smin + m);
     uint32_t* vote = reinterpret_cast<uint32_t*>(smem + ((((size_t)8 * n + 15) & ~(size_t)15) + (size_t)20 * m + 15) / 16 * 16);  // [2][16]
@@ -1241,7 +1217,11 @@ ldpc_ms36_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, int64_t
     constexpr uint32_t REC = 8u * N, MET = REC + 16u * M, VOTE = MET + 4u * M;
     constexpr uint32_t FMASK = 0x80004924u;  // flip bits of positions 0..5: 31, 2, 5, 8, 11, 14
     static_assert(8 * (N - 1) < 65536 && REC % 32 == 0 && MQ >= 1, "ldpc_ms36_kernel geometry");
+    static_assert(REC == ldpc_ms36_rec(N) && MET == ldpc_ms36_meta(N) && (int)VOTE + 128 == ldpc_ms36_lds(N),
+                  "ldpc_plan.hpp describes another layout");
     // static LDS: its base address is the constant 0, so the byte addresses need no base added
+    // (REC, MET and the size are ldpc_ms36_rec / ldpc_ms36_meta / ldpc_ms36_lds of ldpc_plan.hpp,
+    // which the plan's address words ms_vw are built from)
     __shared__ __attribute__((aligned(16))) unsigned char smem[VOTE + 128];
     const int64_t frame = blockIdx.x;
     if (frame >= batch) return;
@@ -1424,11 +1404,6 @@ ldpc_ms36_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, int64_t
     if (iters && tid == 0) iters[frame] = done;
 }
 
-// LDS bytes of ldpc_ms36_kernel<n / 1024> (0: no instance for this code)
-int ldpc_ms36_lds(int n) {
-    return (n == 2048 || n == 4096 || n == 8192) ? 18 * n + 128 : 0;
-}
-
 #if PL_DIAG
 // Thread-per-check kernel: one workgroup (256 threads) per frame, all state in
 // LDS: C[E] (check-to-variable), T[E] (check inputs), tot[n].  Checks are
@@ -1451,7 +1426,7 @@ ldpc_check_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, int64_
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, nt = blockDim.x;
     const int E = g.E, n = g.n, m = g.m;
-    double* C = reinterpret_cast<double*>(smem);
+    double* C = reinterpret_cast<double*>(smem);  // sized by ldpc_check_lds (ldpc_plan.hpp)
     double* T = C + E;
     double* tot = T + E;
     const int32_t* __restrict__ rp = dv.row_ptr;
@@ -1523,10 +1498,6 @@ ldpc_check_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, int64_
 
 #endif  // PL_DIAG
 
-size_t ldpc_work_bytes_per_frame(const LdpcGeom& g) {
-    return g.use_global ? (size_t)(2 * (size_t)g.E) * sizeof(double) : 0;
-}
-
 template <int ALGO>
 static void* pick(bool global) {
 #if PL_DIAG
@@ -1552,10 +1523,7 @@ static void* pick_kernel(const LdpcGeom& g) {
         }
         return g.n <= 8192 ? (void*)ldpc_ms_compact_kernel<8, 0, 0> : (void*)ldpc_ms_compact_kernel<0, 0, 0>;
     }
-    if (g.reg_variant) {
-        int cnt;
-        return reg_table(cnt)[g.reg_variant - 1].k[g.algo != 0 ? 1 : (g.grp ? (g.fpg == 2 ? 3 : 2) : 0)];
-    }
+    if (g.reg_variant) return reg_kernels_of(g.reg_variant).k[g.algo != 0 ? 1 : (g.grp ? (g.fpg == 2 ? 3 : 2) : 0)];
 #if PL_DIAG
     if (g.check_kernel) return g.algo == 0 ? (void*)ldpc_check_kernel<0> : (void*)ldpc_check_kernel<1>;
 #endif

@@ -30,8 +30,6 @@
 #include "common.hpp"
 #include "internal.hpp"
 
-#include <algorithm>
-
 namespace pl {
 
 struct LmsCheck {
@@ -78,8 +76,10 @@ PL_DEV void lms_sync() {
     }
 }
 
-// OR of `pred` over the workgroup behind one barrier (ldpc.hip's wg_any):
-// words[parity][wavefront], double-buffered by the iteration parity.
+// OR of `pred` over the workgroup behind one barrier, words[parity][wavefront]
+// double-buffered by the iteration parity, as ldpc.hip's wg_any -- but that one
+// reads the words four at a time and so needs a multiple of four wavefronts;
+// a layered workgroup has any number from 1 to 16, so this reads them singly.
 PL_DEV bool lms_wg_any(bool pred, uint32_t* words, int parity) {
     const bool any_w = __ballot(pred) != 0;
     if (__lane_id() == 0) words[parity * 16 + (threadIdx.x >> 6)] = any_w ? 1u : 0u;
@@ -204,27 +204,6 @@ ldpc_layered_kernel(LmsGeom g, LmsDev dv, const double* __restrict__ llr, int64_
 static void* lms_pick(const LmsGeom& g) {
     if (g.wave) return g.use_global ? (void*)ldpc_layered_kernel<true, true> : (void*)ldpc_layered_kernel<true, false>;
     return g.use_global ? (void*)ldpc_layered_kernel<false, true> : (void*)ldpc_layered_kernel<false, false>;
-}
-
-// Mapping and state layout for the code described by the fields already set
-// (m, n, maxdc, max_layer); force_global: the PL_LMS_GLOBAL diagnostic switch.
-void lms_geom(LmsGeom* g, bool force_global) {
-    constexpr int kLdsMax = 160 * 1024;
-    g->mw = g->maxdc <= 16 ? 1 : 1 + (g->maxdc + 31) / 32;
-    g->off_mm = (int64_t)(((size_t)8 * g->n + 15) & ~(size_t)15);
-    g->off_meta = g->off_mm + (int64_t)16 * g->m;
-    g->state_bytes = (int64_t)(((size_t)g->off_meta + (size_t)4 * g->m * g->mw + 15) & ~(size_t)15);
-    g->wave = g->max_layer <= 64 ? 1 : 0;
-    const int vote = g->wave ? 0 : 128;
-    g->use_global = (force_global || g->state_bytes + vote > kLdsMax) ? 1 : 0;
-    if (g->wave) {
-        g->fpb = g->use_global ? 4 : (int)std::max<int64_t>(1, std::min<int64_t>(4, 65536 / g->state_bytes));
-        g->threads = 64 * g->fpb;
-    } else {
-        g->fpb = 1;
-        g->threads = std::min(1024, (g->max_layer + 63) / 64 * 64);
-    }
-    g->lds_bytes = (g->use_global ? 0 : (int)g->state_bytes * g->fpb) + vote;
 }
 
 hipError_t lms_prepare(const LmsGeom& g) {

@@ -59,6 +59,12 @@ int main() {
     rp_deg1 = {0, 1, 5};
     EXPECT(pl_ldpc_plan_create(2, 4, rp_deg1.data(), ci_deg1.data(), PL_LDPC_MS, 20, 1, 1.0, 0, &p) ==
            PL_EUNSUPPORTED);  // reference MSDecoder: ValueError on a degree-1 check
+    // a middle row_ptr entry past the end, then a descending one: refused before col_idx is read there
+    std::vector<int32_t> rp_past = {0, 7, 6}, rp_far = {0, 1000, 6}, ci8 = {0, 1, 2, 3, 4, 5};
+    EXPECT(pl_ldpc_plan_create(2, 8, rp_past.data(), ci8.data(), PL_LDPC_BP, 20, 1, 1.0, 0, &p) == PL_EINVAL &&
+           std::strstr(pl_last_error(), "monotone"));
+    EXPECT(pl_ldpc_plan_create(2, 8, rp_far.data(), ci8.data(), PL_LDPC_MS, 20, 1, 1.0, 0, &p) == PL_EINVAL &&
+           std::strstr(pl_last_error(), "monotone"));
     rc = pl_ldpc_plan_create(2, 4, rp.data(), ci.data(), PL_LDPC_BP, 20, 1, 1.0, 0, &p);
     EXPECT(rc == PL_OK || rc == PL_EHIP || rc == PL_ENOMEM);
     if (rc == PL_OK) pl_plan_destroy(p);
