@@ -20,6 +20,7 @@
 //                                        channel LLRs in registers, BP tanh via a
 //                                        compacted work list (the BASELINE codes);
 //   ldpc_decode_kernel<ALGO, GLOBAL, ..> any code, LDS or global-workspace state;
+//                                        BP with libm's tanh / atanh bit for bit;
 //   ldpc_ms_compact_kernel               min-sum for codes whose T/C exceed LDS:
 //                                        compressed per-check statistics in LDS;
 //   ldpc_ms36_kernel<VPT>                the same for (3,6)-regular n = 1024 VPT
@@ -28,6 +29,7 @@
 #include "common.hpp"
 #include "internal.hpp"
 #include "fp64_math.hpp"
+#include "libm_exact.hpp"
 
 #include <cstdlib>
 #include <string>
@@ -189,7 +191,8 @@ ldpc_decode_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, int64
     const double* __restrict__ ch = llr + frame * ld;
     auto tin = [&](double x) -> double {
         if (ALGO != 0) return x;
-        return OCML ? clip999(tanh(x / 2.0)) : tanh_half_clip(x);
+        // libm's tanh / atanh bit for bit (libm_exact.hpp): the oracle's, whatever the code
+        return clip999(OCML ? tanh(x / 2.0) : libm_tanh(x / 2.0));
     };
 
     for (int c = tid; c < 2 * m; c += nt) syn[c] = 0u;
@@ -232,7 +235,7 @@ ldpc_decode_kernel(LdpcGeom g, LdpcDev dv, const double* __restrict__ llr, int64
                 for (; k < nf; ++k, ++lo, ++hi) p *= (k < i ? lo : hi)[0];
                 const bool pn = __builtin_isnan(p);
                 p = __builtin_fmax(__builtin_fmin(p, 0.999999), -0.999999);
-                o = OCML ? 2.0 * atanh(p) : two_atanh(p);
+                o = 2.0 * (OCML ? atanh(p) : libm_atanh(p));
                 o = pn ? 0.0 : o;  // nan_to_num; 2*atanh is finite after the clip
             } else {
                 o = ms_check(T + e0, i, d, g.norm);

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import golden
+from ldpc_codes import special_llrs as _special_llrs
 
 pytestmark = pytest.mark.gpu
 
@@ -97,25 +98,6 @@ def test_ms_8192(gpu, kernel, monkeypatch):
     else:
         assert dec.plan.info.reserved == (8 if kernel == "default" else 5)
     assert np.array_equal(dec.decode_batch(d["llr"]), d["ms_0_75"])
-
-
-def _special_llrs(rng, B, n):
-    """Noisy all-zero-codeword LLRs with the special values of min-sum's check
-    statistics: exact zeros (one or many per check), -0, +-inf, NaN (one, a few)."""
-    snr = rng.uniform(0.5, 2.5, size=(B, 1))
-    sigma = np.sqrt(1.0 / (2.0 * 10 ** (snr / 10.0)))
-    llr = 2.0 * (1.0 + sigma * rng.randn(B, n)) / sigma ** 2
-    llr[1, ::5] = 0.0
-    llr[2, ::97] = -0.0
-    llr[3, 7] = np.nan
-    llr[4, 11], llr[4, 12] = np.inf, -np.inf
-    llr[5, :3] = np.nan
-    llr[6, rng.rand(n) < 0.3] = 0.0          # erasures: checks with 1, 2 or more zeros
-    llr[7, rng.rand(n) < 0.02] = np.nan      # scattered NaN
-    llr[8, rng.rand(n) < 0.1] = np.inf
-    llr[8, rng.rand(n) < 0.1] = -np.inf
-    llr[9, :] = np.where(rng.rand(n) < 0.5, 0.0, -0.0)
-    return llr
 
 
 @pytest.mark.parametrize("kernel", ["default", "compact"])
