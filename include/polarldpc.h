@@ -46,14 +46,18 @@ typedef struct {
                            wavefront; flooding LDPC, 2 on the degree-grouped BP
                            kernel's two-frame instance, else 1; layered LDPC,
                            frames per workgroup (one wavefront each), 1 when a
-                           workgroup decodes one frame                             */
+                           workgroup decodes one frame; quasi-cyclic layered LDPC,
+                           frames per workgroup (64 / Z per wavefront for Z <= 64) */
     int32_t reserved;   /* polar: kernel (4 tree, 3 lane, 6 single-workgroup exact);
                            LDPC: 2 register-cached, 7 register-cached BP with
                            degree-grouped check products, 1 generic,
                            3 thread-per-check, 5 min-sum with compressed check state,
                            8 (3,6)-regular min-sum with rebuild-ready check state,
                            9 layered min-sum with its state in LDS,
-                           10 layered min-sum with its state in the workspace       */
+                           10 layered min-sum with its state in the workspace,
+                           11 quasi-cyclic layered min-sum with its state in LDS,
+                           12 quasi-cyclic layered min-sum with its state in the
+                           workspace                                                */
 } pl_plan_info;
 
 /* Polar SC / SCL plan.
@@ -131,6 +135,32 @@ int pl_ldpc_layered_plan_create(int32_t m, int32_t n, const int32_t* row_ptr, co
                                 int32_t max_iter, int32_t early_stop, double normalization, int32_t flags,
                                 pl_plan** out);
 
+/* Quasi-cyclic layered normalised min-sum plan.  Build-defined, as the layered
+ *   plan.  H is mb x nb blocks of z x z: shift[i * nb + j] (host array, row-major)
+ *   is -1 for a zero block, else s in 0 .. z-1 for the cyclically shifted identity
+ *   H[i z + r, j z + (r + s) % z] = 1, r = 0 .. z-1 (one circulant per block).
+ *   The decoder is by definition pl_ldpc_layered_plan_create's on that H with
+ *   the block rows as layers, layer l = rows [i z, (i+1) z) for i = layer_order[l]
+ *   (host array [mb], a permutation of 0 .. mb-1; NULL: 0 .. mb-1): same bits,
+ *   iteration counts and posteriors, bit for bit.  H is never expanded.
+ *   PL_EINVAL for mb, nb or z < 1, nb z or mb z beyond int32, a shift outside
+ *   -1 .. z-1, a layer_order that is no permutation, max_iter < 0;
+ *   PL_EUNSUPPORTED for a block row with exactly one non-zero block when
+ *   max_iter > 0 (as the layered plan's degree-1 row), a block row with >= 2048
+ *   non-zero blocks, z > 1024.  A block row without blocks is skipped.  Every
+ *   argument check runs before the first device call.
+ *   One thread updates one check of the current block row; for z <= 64, 64 / z
+ *   frames share a wavefront (each stops on its own zero syndrome), otherwise
+ *   one workgroup of z threads (rounded up to 64) decodes a frame.  The state
+ *   (as the layered plan's) lives in LDS when it fits 160 KB
+ *   (pl_plan_info.reserved 11), else in the workspace (12); PL_LMS_GLOBAL=1
+ *   forces the workspace.  pl_decode, pl_decode_ws, pl_ldpc_decode_soft,
+ *   pl_plan_workspace_bytes, pl_plan_reserve and pl_plan_release work as for a
+ *   layered plan. */
+int pl_ldpc_qc_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift /* [mb*nb] row-major */,
+                           const int32_t* layer_order /* [mb] or NULL */, int32_t max_iter, int32_t early_stop,
+                           double normalization, int32_t flags, pl_plan** out);
+
 /* Batched decode: replaces SCDecoder.decode (decoder.py:38-71),
  *   SCLDecoder.decode (:225-262), BPDecoder.decode (src/ldpc/decoder.py:124-202)
  *   and MSDecoder.decode (:289-352) applied to `batch` frames.
@@ -164,7 +194,7 @@ int pl_plan_workspace_bytes(const pl_plan* plan, int64_t batch, int64_t* bytes);
 int pl_decode_ws(pl_plan* plan, const double* llr_dev, int64_t batch, int64_t ld, uint8_t* bits_dev,
                  int32_t* iters_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
 
-/* pl_decode of a layered min-sum plan that also writes the final posteriors
+/* pl_decode of a layered (or quasi-cyclic layered) min-sum plan that also writes the final posteriors
  * P (the state the decisions are taken from: bits = P <= 0) to post_dev, fp64
  * [batch][ld_post] device, ld_post >= n.  Bits, iteration counts and posteriors
  * are reproducible bit for bit (no transcendental is involved; NaN payloads
@@ -300,6 +330,23 @@ int pl_debug_ldpc_layered_plan_probe(int32_t m, int32_t n, const int32_t* row_pt
                                      int32_t max_iter, int32_t early_stop, double normalization,
                                      int32_t kernel_override, int32_t bp_fpg, int32_t lms_global,
                                      pl_ldpc_layered_plan_probe* out);
+
+/* The same for pl_ldpc_qc_plan_create (no kernel_override / bp_fpg: they do not
+ * apply).  fpw: frames per wavefront; fpb: wavefronts per workgroup when z <= 64,
+ * else 1, so a workgroup decodes fpw * fpb frames; dcap: the inputs of a check
+ * the kernel instance keeps in registers (8, 16, 32; 0: the two-pass instance);
+ * table_len / digest: the layer stream (per layer the block row, its degree and
+ * its (block column, shift) pairs). */
+typedef struct {
+    int32_t kernel;      /* 11 or 12, as pl_plan_info.reserved */
+    int32_t z, mb, nb, maxdc, dcap, mw, fpw, fpb, threads, lds_bytes, use_global;
+    int64_t state_bytes;
+    int64_t table_len;
+    uint64_t digest;
+} pl_ldpc_qc_plan_probe;
+int pl_debug_ldpc_qc_plan_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift, const int32_t* layer_order,
+                                int32_t max_iter, int32_t early_stop, double normalization, int32_t lms_global,
+                                pl_ldpc_qc_plan_probe* out);
 
 /* ---- Monte-Carlo frame source (replaces src/channel/awgn.py:91-112 and the
  *      message/encode loop of benchmarks/ber_simulation.py:167-177) ---------- */

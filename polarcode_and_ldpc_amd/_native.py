@@ -26,7 +26,8 @@ EXPORTS = (
     "pl_rayleigh_llr", "pl_bsc", "pl_gf2_encode", "pl_decode_ws", "pl_plan_workspace_bytes",
     "pl_plan_release", "pl_plan_workspace_stats", "pl_debug_set_plan_device", "pl_debug_polar_fpw",
     "pl_debug_polar_flagged", "pl_polar_plan_small_batch", "pl_ldpc_layered_plan_create", "pl_ldpc_decode_soft",
-    "pl_debug_ldpc_plan_probe", "pl_debug_ldpc_layered_plan_probe",
+    "pl_debug_ldpc_plan_probe", "pl_debug_ldpc_layered_plan_probe", "pl_ldpc_qc_plan_create",
+    "pl_debug_ldpc_qc_plan_probe",
 )
 
 
@@ -52,6 +53,14 @@ class LdpcLayeredPlanProbe(ctypes.Structure):
                [("digest", ctypes.c_uint64)]
 
 
+class LdpcQcPlanProbe(ctypes.Structure):
+    """pl_ldpc_qc_plan_probe: the quasi-cyclic layered kernel's geometry."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("kernel", "z", "mb", "nb", "maxdc", "dcap", "mw", "fpw", "fpb", "threads",
+                                              "lds_bytes", "use_global")] + \
+               [(f, ctypes.c_int64) for f in ("state_bytes", "table_len")] + \
+               [("digest", ctypes.c_uint64)]
+
+
 def _load(path=LIB_PATH):
     if not os.path.exists(path):
         raise ImportError(
@@ -67,6 +76,8 @@ def _load(path=LIB_PATH):
     L.pl_debug_ldpc_plan_probe.argtypes = [I32, I32, P, P, I32, I32, I32, D, I32, I32, I32, ctypes.POINTER(LdpcPlanProbe)]
     L.pl_debug_ldpc_layered_plan_probe.argtypes = [I32, I32, P, P, I32, P, P, I32, I32, D, I32, I32, I32,
                                                    ctypes.POINTER(LdpcLayeredPlanProbe)]
+    L.pl_ldpc_qc_plan_create.argtypes = [I32, I32, I32, P, P, I32, I32, D, I32, PP]
+    L.pl_debug_ldpc_qc_plan_probe.argtypes = [I32, I32, I32, P, P, I32, I32, D, I32, ctypes.POINTER(LdpcQcPlanProbe)]
     L.pl_ldpc_decode_soft.argtypes = [P, P, I64, I64, P, P, P, I64, P]
     L.pl_decode.argtypes = [P, P, I64, I64, P, P, P]
     L.pl_plan_reserve.argtypes = [P, I64, P]
@@ -306,6 +317,23 @@ def layered_ldpc_plan(row_ptr: np.ndarray, col_idx: np.ndarray, n: int, layers, 
                                           lp.ctypes.data_as(ctypes.c_void_p), lr.ctypes.data_as(ctypes.c_void_p),
                                           int(max_iter), int(bool(early_stop)), float(normalization), 0,
                                           ctypes.byref(h)), "pl_ldpc_layered_plan_create")
+    return Plan(h)
+
+
+def qc_ldpc_plan(base: np.ndarray, Z: int, layer_order, max_iter: int, early_stop: bool,
+                 normalization: float = 1.0) -> Plan:
+    """Quasi-cyclic layered min-sum plan (pl_ldpc_qc_plan_create); base: int [mb, nb]
+    shifts (-1: zero block); layer_order: a permutation of the block rows or None."""
+    sh = np.ascontiguousarray(base, dtype=np.int32)
+    assert sh.ndim == 2, "base must be [mb, nb]"
+    lo = None if layer_order is None else np.ascontiguousarray(layer_order, dtype=np.int32).ravel()
+    assert lo is None or len(lo) == sh.shape[0], "layer_order must list the mb block rows"
+    require_gpu()
+    h = ctypes.c_void_p()
+    check(lib.pl_ldpc_qc_plan_create(sh.shape[0], sh.shape[1], int(Z), sh.ctypes.data_as(ctypes.c_void_p),
+                                     None if lo is None else lo.ctypes.data_as(ctypes.c_void_p), int(max_iter),
+                                     int(bool(early_stop)), float(normalization), 0, ctypes.byref(h)),
+          "pl_ldpc_qc_plan_create")
     return Plan(h)
 
 

@@ -6,6 +6,6 @@ _ROOT = str(_Path(__file__).resolve().parents[4])
 if _ROOT not in _sys.path:
     _sys.path.insert(0, _ROOT)
 
-from polarcode_and_ldpc_amd.ldpc.decoder import BPDecoder, LayeredMSDecoder, MSDecoder  # noqa: F401
+from polarcode_and_ldpc_amd.ldpc.decoder import BPDecoder, LayeredMSDecoder, MSDecoder, QCLayeredMSDecoder  # noqa: F401
 
-__all__ = ['BPDecoder', 'MSDecoder', 'LayeredMSDecoder']
+__all__ = ['BPDecoder', 'MSDecoder', 'LayeredMSDecoder', 'QCLayeredMSDecoder']

@@ -68,6 +68,10 @@ struct pl_plan {
     bool layered = false;
     pl::LmsGeom lms{};
     pl::LmsDev lmsd{};
+    // quasi-cyclic layered min-sum (ldpc_qc_layered.hip): a layered plan (lms.n, lms.m set) whose
+    // kernel geometry is qcg and whose table buffer is the layer stream
+    bool qc = false;
+    pl::QcGeom qcg{};
     // workspace: bytes per unit (polar: one resident wave; LDPC global: one
     // frame), one buffer per stream (plans are shared across host threads that
     // use distinct streams; a decode only ever touches its stream's buffer)
@@ -372,6 +376,31 @@ extern "C" int pl_ldpc_layered_plan_create(int32_t m, int32_t n, const int32_t* 
     return PL_OK;
 }
 
+extern "C" int pl_ldpc_qc_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                      const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
+                                      double normalization, int32_t flags, pl_plan** out) {
+    (void)flags;
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    *out = nullptr;
+    // every argument check (ldpc_plan.cpp) comes before the first device call
+    pl::QcHostPlan hp;
+    const pl::PlanStatus st = pl::qc_plan_build(mb, nb, z, shift, layer_order, max_iter, early_stop, normalization,
+                                                ldpc_env_options(), &hp);
+    if (st.code) return fail(st.code, st.msg);
+    pl_plan* p;
+    if (int rc = ldpc_plan_upload(hp.tables, &p)) return rc;
+    p->layered = true;
+    p->qc = true;
+    p->qcg = hp.geom;
+    p->lg.n = p->lms.n = hp.geom.n;
+    p->lg.m = p->lms.m = hp.geom.m;
+    const hipError_t e = pl::qc_prepare(p->qcg);
+    if (e != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "hipFuncSetAttribute"); }
+    p->ws_unit = p->qcg.use_global ? (size_t)p->qcg.state_bytes : 0;
+    *out = p;
+    return PL_OK;
+}
+
 // The planner's decisions for a code, with no plan object and no device call.
 extern "C" int pl_debug_ldpc_plan_probe(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
                                         int32_t algo, int32_t max_iter, int32_t early_stop, double normalization,
@@ -406,6 +435,21 @@ extern "C" int pl_debug_ldpc_layered_plan_probe(int32_t m, int32_t n, const int3
     *out = pl_ldpc_layered_plan_probe{pl::lms_kernel_code(g), g.maxdc, g.n_layers, g.max_layer, g.mw, g.wave,
                                       g.use_global, g.fpb, g.threads, g.lds_bytes, g.state_bytes, g.off_mm, g.off_meta,
                                       (int64_t)hp.tables.size(), pl::plan_tables_digest(hp.tables)};
+    return PL_OK;
+}
+
+extern "C" int pl_debug_ldpc_qc_plan_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                           const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
+                                           double normalization, int32_t lms_global, pl_ldpc_qc_plan_probe* out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    pl::QcHostPlan hp;
+    const pl::PlanStatus st = pl::qc_plan_build(mb, nb, z, shift, layer_order, max_iter, early_stop, normalization,
+                                                ldpc_options(0, 0, lms_global), &hp);
+    if (st.code) return fail(st.code, st.msg);
+    const pl::QcGeom& g = hp.geom;
+    *out = pl_ldpc_qc_plan_probe{pl::qc_kernel_code(g), g.z, g.mb, g.nb, g.maxdc, g.dcap, g.mw, g.fpw, g.fpb,
+                                 g.threads, g.lds_bytes, g.use_global, g.state_bytes, (int64_t)hp.tables.size(),
+                                 pl::plan_tables_digest(hp.tables)};
     return PL_OK;
 }
 
@@ -456,9 +500,13 @@ static int lms_decode_impl(pl_plan* p, const double* llr, int64_t batch, int64_t
                                         : kMaxLaunchItems / 1024;
     for (int64_t b0 = 0; b0 < batch; b0 += step) {
         const int64_t nb = std::min<int64_t>(step, batch - b0);
-        hipError_t e = pl::lms_launch(p->lms, p->lmsd, llr + b0 * ld, ld, bits + b0 * p->lms.n,
-                                      iters ? iters + b0 : nullptr, post ? post + b0 * ld_post : nullptr, ld_post, nb,
-                                      (unsigned char*)ws, s);
+        uint8_t* const bo = bits + b0 * p->lms.n;
+        int32_t* const io = iters ? iters + b0 : nullptr;
+        double* const po = post ? post + b0 * ld_post : nullptr;
+        hipError_t e = p->qc ? pl::qc_launch(p->qcg, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
+                                             (unsigned char*)ws, s)
+                             : pl::lms_launch(p->lms, p->lmsd, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
+                                              (unsigned char*)ws, s);
         if (e != hipSuccess) return hipfail(e, "layered ldpc decode launch");
     }
     return PL_OK;
@@ -879,6 +927,10 @@ extern "C" int pl_plan_get_info(const pl_plan* p, pl_plan_info* info) {
         info->kind = 1; info->n_in = p->lms.n; info->n_out = p->lms.n; info->list_size = 0;
         info->lds_bytes = p->lms.lds_bytes; info->fused_top = 0; info->frames_per_block = p->lms.fpb;
         info->reserved = pl::lms_kernel_code(p->lms);  // layered min-sum: 9 state in LDS, 10 in the workspace
+        if (p->qc) {  // quasi-cyclic layered min-sum: 11 state in LDS, 12 in the workspace
+            info->lds_bytes = p->qcg.lds_bytes; info->frames_per_block = p->qcg.fpw * p->qcg.fpb;
+            info->reserved = pl::qc_kernel_code(p->qcg);
+        }
     } else {
         info->kind = 1; info->n_in = p->lg.n; info->n_out = p->lg.n; info->list_size = 0;
         info->lds_bytes = p->lg.lds_bytes; info->fused_top = 0; info->frames_per_block = p->lg.fpg > 1 ? p->lg.fpg : 1;

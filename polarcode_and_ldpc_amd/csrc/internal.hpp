@@ -134,4 +134,10 @@ hipError_t lms_prepare(const LmsGeom& g);
 hipError_t lms_launch(const LmsGeom& g, const LmsDev& d, const double* llr, int64_t ld, uint8_t* bits, int32_t* iters,
                       double* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
 
+// ---- quasi-cyclic layered min-sum (ldpc_qc_layered.hip); QcGeom: ldpc_plan.hpp ----
+hipError_t qc_prepare(const QcGeom& g);
+// tab: the plan's layer stream (device); the other arguments as lms_launch
+hipError_t qc_launch(const QcGeom& g, const int32_t* tab, const double* llr, int64_t ld, uint8_t* bits, int32_t* iters,
+                     double* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
+
 }  // namespace pl

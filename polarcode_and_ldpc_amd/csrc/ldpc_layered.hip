@@ -27,68 +27,13 @@
 // pre-scaled min could overflow or lose a NaN.  Posteriors therefore equal the
 // NumPy definition bit for bit.  Row degrees up to 2047 (11-bit positions).
 // The state lives in LDS, or (GLOBAL) in a per-frame slice of the workspace.
+// The check state and its helpers are in ldpc_lms_check.hpp (shared with
+// ldpc_qc_layered.hip).
 #include "common.hpp"
 #include "internal.hpp"
+#include "ldpc_lms_check.hpp"
 
 namespace pl {
-
-struct LmsCheck {
-    double min1, min2;
-    uint32_t idx1, nidx, ncnt, zcnt, par;
-};
-
-// Meta word of a check.  mw == 1 (every degree <= 16): idx1 bits 0-3, nidx 4-7,
-// NaN count 8-9 and zero count 10-11 (saturating at 2), parity 12, negative
-// flags 16-31.  mw > 1: idx1 0-10, nidx 11-21, NaN count 22-23, zero count
-// 24-25, parity 26; the flags follow in mw - 1 words of 32 positions.
-PL_DEV uint32_t lms_pack(const LmsCheck& s, bool small, uint32_t negs) {
-    return small ? (s.idx1 | (s.nidx << 4) | (s.ncnt << 8) | (s.zcnt << 10) | (s.par << 12) | (negs << 16))
-                 : (s.idx1 | (s.nidx << 11) | (s.ncnt << 22) | (s.zcnt << 24) | (s.par << 26));
-}
-PL_DEV void lms_unpack(uint32_t w, bool small, LmsCheck& s) {
-    if (small) {
-        s.idx1 = w & 15u; s.nidx = (w >> 4) & 15u; s.ncnt = (w >> 8) & 3u; s.zcnt = (w >> 10) & 3u; s.par = (w >> 12) & 1u;
-    } else {
-        s.idx1 = w & 2047u; s.nidx = (w >> 11) & 2047u; s.ncnt = (w >> 22) & 3u; s.zcnt = (w >> 24) & 3u; s.par = (w >> 26) & 1u;
-    }
-}
-
-// R_cj from the state of check c over all its inputs; `neg` = input j was
-// negative.  The sign product over k != j is +-1 by the parity of negatives,
-// +-0 if another input is zero (a single zero is the smallest input, idx1),
-// NaN if another input is NaN; the min over k != j is min2 at idx1, else min1.
-PL_DEV double lms_c2v(const LmsCheck& s, uint32_t neg, uint32_t j, double norm) {
-    const double mn = (j == s.idx1) ? s.min2 : s.min1;
-    double sp = ((s.par ^ neg) & 1u) ? -1.0 : 1.0;
-    sp = (s.zcnt >= 2u || (s.zcnt == 1u && s.idx1 != j)) ? sp * 0.0 : sp;
-    sp = (s.ncnt >= 2u || (s.ncnt == 1u && s.nidx != j)) ? __builtin_nan("") : sp;
-    return (sp * mn) * norm;
-}
-
-template <bool WAVE>
-PL_DEV void lms_sync() {
-    if (WAVE) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-        __syncthreads();
-    }
-}
-
-// OR of `pred` over the workgroup behind one barrier, words[parity][wavefront]
-// double-buffered by the iteration parity, as ldpc.hip's wg_any -- but that one
-// reads the words four at a time and so needs a multiple of four wavefronts;
-// a layered workgroup has any number from 1 to 16, so this reads them singly.
-PL_DEV bool lms_wg_any(bool pred, uint32_t* words, int parity) {
-    const bool any_w = __ballot(pred) != 0;
-    if (__lane_id() == 0) words[parity * 16 + (threadIdx.x >> 6)] = any_w ? 1u : 0u;
-    __syncthreads();
-    uint32_t any = 0;
-    const int nw = (blockDim.x + 63) >> 6;
-    for (int k = 0; k < nw; ++k) any |= words[parity * 16 + k];
-    return any != 0u;
-}
 
 // One layered update of check c (degree d >= 2).  Two passes over its inputs:
 // the first forms q_j and the new state, the second forms q_j again (P and the

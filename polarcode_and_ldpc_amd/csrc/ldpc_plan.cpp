@@ -2,7 +2,8 @@
 // environment read.  Flooding plans: CSR checks, the degree sort and adjacency
 // tables, kernel selection, the degree-grouped BP tables, the (3,6) min-sum
 // address words, all packed into one vector.  Layered plans: layer checks and
-// the kernel geometry.
+// the kernel geometry.  Quasi-cyclic layered plans: base-matrix checks, the
+// geometry and the per-layer (block column, shift) stream.
 #include "ldpc_plan.hpp"
 
 #include <algorithm>
@@ -421,6 +422,91 @@ PlanStatus lms_plan_build(int m, int n, const int32_t* row_ptr, const int32_t* c
     all.insert(all.end(), col_idx, col_idx + csr.E);
     all.insert(all.end(), layer_ptr, layer_ptr + n_layers + 1);
     all.insert(all.end(), layer_rows, layer_rows + m);
+    return {};
+}
+
+// ---- quasi-cyclic layered plans ----
+
+PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order, int max_iter,
+                         int early_stop, double norm, const LdpcPlanOptions& opt, QcHostPlan* out) {
+    constexpr int kLdsMax = 160 * 1024;
+    if (mb < 1 || nb < 1 || z < 1 || !shift) return refuse(PL_EINVAL, "mb, nb and Z must be >= 1");
+    if ((int64_t)nb * z > INT32_MAX || (int64_t)mb * z > INT32_MAX)
+        return refuse(PL_EINVAL, "nb Z and mb Z must fit 32 bits");
+    if (max_iter < 0) return refuse(PL_EINVAL, "max_iter must be >= 0");
+    int maxdc = 0;
+    bool deg1 = false;
+    size_t blocks = 0;
+    for (int i = 0; i < mb; ++i) {
+        int d = 0;
+        for (int j = 0; j < nb; ++j) {
+            const int s = shift[(size_t)i * nb + j];
+            if (s < -1 || s >= z)
+                return refuse(PL_EINVAL, "shift of block (" + std::to_string(i) + ", " + std::to_string(j) +
+                                             ") outside -1 .. Z-1");
+            d += s >= 0;
+        }
+        maxdc = std::max(maxdc, d);
+        deg1 |= d == 1;
+        blocks += (size_t)d;
+    }
+    std::vector<int32_t> order((size_t)mb);
+    if (layer_order) {
+        std::vector<uint8_t> seen((size_t)mb, 0);
+        for (int l = 0; l < mb; ++l) {
+            const int i = layer_order[l];
+            if (i < 0 || i >= mb || seen[i]) return refuse(PL_EINVAL, "layer_order must be a permutation of 0 .. mb-1");
+            seen[i] = 1;
+            order[l] = i;
+        }
+    } else {
+        for (int l = 0; l < mb; ++l) order[l] = l;
+    }
+    // max_iter == 0 evaluates no check, as in the layered plan
+    if (deg1 && max_iter > 0)
+        return refuse(PL_EUNSUPPORTED, "min-sum on a degree-1 check (reference raises ValueError)");
+    if (maxdc >= (1 << 11)) return refuse(PL_EUNSUPPORTED, "check degree >= 2048");
+    if (z > kQcMaxZ) return refuse(PL_EUNSUPPORTED, "Z > 1024");
+
+    LmsGeom lg{};  // the state layout is the layered kernel's
+    lg.m = mb * z; lg.n = nb * z; lg.maxdc = maxdc; lg.max_layer = z;
+    lms_geom(&lg, opt.lms_global);
+    QcGeom& g = out->geom;
+    g = QcGeom{};
+    g.mb = mb; g.nb = nb; g.z = z; g.m = lg.m; g.n = lg.n; g.max_iter = max_iter; g.early_stop = early_stop ? 1 : 0;
+    g.maxdc = maxdc; g.norm = norm; g.mw = lg.mw;
+    g.dcap = maxdc <= 8 ? 8 : maxdc <= 16 ? 16 : maxdc <= kQcDcapMax ? 32 : 0;
+    g.state_bytes = lg.state_bytes; g.off_mm = lg.off_mm; g.off_meta = lg.off_meta;
+    g.subwave = z <= 64 ? 1 : 0;
+    if (g.subwave) {
+        // fpw frames side by side in a wavefront's lanes; the LDS bound of lms_geom's WAVE case, per wavefront
+        g.fpw = 64 / z;
+        const int64_t wave_state = g.state_bytes * g.fpw;
+        g.use_global = (opt.lms_global || wave_state > kLdsMax) ? 1 : 0;
+        g.fpb = g.use_global ? 4 : (int)std::max<int64_t>(1, std::min<int64_t>(4, 65536 / wave_state));
+        g.threads = 64 * g.fpb;
+        g.lds_bytes = g.use_global ? 0 : (int)(wave_state * g.fpb);
+    } else {
+        g.fpw = 1;
+        g.fpb = 1;
+        g.use_global = (opt.lms_global || g.state_bytes + kLdpcVoteBytes > kLdsMax) ? 1 : 0;
+        g.threads = (z + 63) / 64 * 64;
+        g.lds_bytes = (g.use_global ? 0 : (int)g.state_bytes) + kLdpcVoteBytes;
+    }
+    std::vector<int32_t>& t = out->tables;
+    t.clear();
+    t.reserve(2 * (size_t)mb + 2 * blocks);
+    for (int l = 0; l < mb; ++l) {
+        const int i = order[l];
+        const size_t at = t.size();
+        t.push_back(i);
+        t.push_back(0);
+        for (int j = 0; j < nb; ++j) {
+            const int s = shift[(size_t)i * nb + j];
+            if (s >= 0) { t.push_back(j); t.push_back(s); }
+        }
+        t[at + 1] = (int32_t)((t.size() - at - 2) / 2);
+    }
     return {};
 }
 

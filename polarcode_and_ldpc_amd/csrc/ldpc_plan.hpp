@@ -190,6 +190,35 @@ PlanStatus lms_plan_build(int m, int n, const int32_t* row_ptr, const int32_t* c
                           const int32_t* layer_ptr, const int32_t* layer_rows, int max_iter, int early_stop,
                           double norm, const LdpcPlanOptions& opt, LmsHostPlan* out);
 
+// ---- quasi-cyclic layered min-sum (ldpc_qc_layered.hip) ----
+// H is mb x nb blocks of z x z, each zero or a cyclically shifted identity; a
+// block row is a layer.  State layout per frame: lms_geom's.
+struct QcGeom {
+    int mb, nb, z, m, n, max_iter, early_stop, maxdc;
+    double norm;
+    int mw;          // meta words per check, as LmsGeom::mw
+    int dcap;        // inputs of a check kept in registers: 8, 16 or 32 (>= maxdc); 0: two-pass form
+    int subwave;     // 1 (z <= 64): fpw frames share a wavefront; 0: one workgroup per frame
+    int use_global;  // state in the workspace instead of LDS
+    int fpw;         // frames per wavefront (64 / z; 1 when !subwave)
+    int fpb;         // wavefronts per workgroup when subwave, else 1: a workgroup decodes fpw fpb frames
+    int threads, lds_bytes;
+    int64_t state_bytes, off_mm, off_meta;
+};
+constexpr int kQcMaxZ = 1024;
+constexpr int kQcDcapMax = 32;  // largest register-resident instance of ldpc_qc_kernel
+inline int qc_kernel_code(const QcGeom& g) { return g.use_global ? 12 : 11; }
+struct QcHostPlan {
+    QcGeom geom{};
+    // per layer, in layer order: block row, its degree d, then d (block column, shift) pairs by
+    // ascending block column -- a stream the kernel walks front to back, 2 + 2 d words a layer
+    std::vector<int32_t> tables;
+};
+// Quasi-cyclic layered min-sum plan (pl_ldpc_qc_plan_create's arguments); shift [mb][nb]
+// row-major, -1 a zero block; layer_order [mb] a permutation of the block rows, or null (0 .. mb-1).
+PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order, int max_iter,
+                         int early_stop, double norm, const LdpcPlanOptions& opt, QcHostPlan* out);
+
 // 64-bit FNV-1a over a table vector's bytes (the pl_debug_*_plan_probe digests)
 uint64_t plan_tables_digest(const std::vector<int32_t>& tables);
 

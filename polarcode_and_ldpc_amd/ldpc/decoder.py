@@ -4,7 +4,8 @@ Same constructors, attributes and `.decode(llr)` contract as the reference's
 src/ldpc/decoder.py (BPDecoder :11-205, MSDecoder :208-355), plus
 `decode_batch` for host or device batches.  No CPU path.
 LayeredMSDecoder (ldpc_layered.hip) is a build-defined extension: the serial
-schedule with posterior LLR output.
+schedule with posterior LLR output; QCLayeredMSDecoder (ldpc_qc_layered.hip) is
+the same decoder for a quasi-cyclic code given by its base matrix.
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from .matrix import dense_to_csr, layer_schedule
+from .matrix import dense_to_csr, layer_schedule, qc_block_layers, qc_expand
 
 
 class _LdpcBase:
@@ -203,3 +204,51 @@ class LayeredMSDecoder(_LdpcBase):
     def __repr__(self) -> str:
         return (f"LayeredMSDecoder(n={self.n}, m={self.m}, max_iter={self.max_iter}, norm={self.normalization}, "
                 f"layers={len(self.layers)})")
+
+
+class QCLayeredMSDecoder(LayeredMSDecoder):
+    """LayeredMSDecoder for a quasi-cyclic code given by its base matrix
+    (ldpc_qc_layered.hip).  `base`: int [mb, nb], -1 a zero Z x Z block, s in
+    0 .. Z-1 the identity shifted cyclically by s (qc_expand).  The layers are
+    the block rows, visited in `layer_order` (default 0 .. mb-1).  By definition
+    equal, bit for bit, to LayeredMSDecoder(qc_expand(base, Z),
+    layers=qc_block_layers(mb, Z, layer_order)); H is never expanded unless `.H`
+    is read."""
+
+    def __init__(self, base: np.ndarray, Z: int, max_iter: int = 50, normalization: float = 1.0,
+                 early_stop: bool = True, layer_order=None):
+        self._algo = _native.PL_LDPC_LMS
+        self.base = np.array(base, dtype=np.int64)
+        assert self.base.ndim == 2, "base must be [mb, nb]"
+        self.Z = int(Z)
+        self.mb, self.nb = self.base.shape
+        self.m, self.n = self.mb * self.Z, self.nb * self.Z
+        self.max_iter = max_iter
+        self.early_stop = early_stop
+        self.normalization = normalization
+        self.layer_order = None if layer_order is None else [int(i) for i in layer_order]
+        self.check_degrees = np.repeat((self.base >= 0).sum(axis=1), self.Z)
+        self.var_neighbors = None
+        self._plan = None
+        self._H = None
+
+    @property
+    def H(self):
+        if self._H is None:
+            self._H = qc_expand(self.base, self.Z)
+        return self._H
+
+    @property
+    def layers(self):
+        return qc_block_layers(self.mb, self.Z, self.layer_order)
+
+    @property
+    def plan(self):
+        if self._plan is None:
+            self._plan = _native.qc_ldpc_plan(self.base, self.Z, self.layer_order, self.max_iter, self.early_stop,
+                                              self.normalization)
+        return self._plan
+
+    def __repr__(self) -> str:
+        return (f"QCLayeredMSDecoder(n={self.n}, m={self.m}, Z={self.Z}, max_iter={self.max_iter}, "
+                f"norm={self.normalization})")

@@ -53,6 +53,63 @@ def layer_schedule(H: np.ndarray) -> list:
     return [np.asarray(l, dtype=np.int64) for l in layers]
 
 
+def _qc_base(base, Z: int) -> np.ndarray:
+    base = np.asarray(base)
+    assert base.ndim == 2 and base.size > 0 and int(Z) >= 1, "base must be [mb, nb] and Z >= 1"
+    assert np.all((base >= -1) & (base < int(Z))), "base entries must lie in -1 .. Z-1"
+    return base.astype(np.int64)
+
+
+def qc_expand(base, Z: int) -> np.ndarray:
+    """Dense H of the quasi-cyclic code (base, Z): base is int [mb, nb], entry -1
+    a zero Z x Z block, entry s in 0 .. Z-1 the identity shifted cyclically by s,
+    H[i Z + r, j Z + (r + s) % Z] = 1.  For tests and small codes; the decoder
+    (QCLayeredMSDecoder) never expands H."""
+    base = _qc_base(base, Z)
+    mb, nb = base.shape
+    H = np.zeros((mb * Z, nb * Z), dtype=int)
+    r = np.arange(Z)
+    for i, j in zip(*np.nonzero(base >= 0)):
+        H[i * Z + r, j * Z + (r + base[i, j]) % Z] = 1
+    return H
+
+
+def qc_to_csr(base, Z: int) -> Tuple[np.ndarray, np.ndarray]:
+    """dense_to_csr(qc_expand(base, Z)) without the dense matrix."""
+    base = _qc_base(base, Z)
+    mb, nb = base.shape
+    deg = (base >= 0).sum(axis=1)
+    row_ptr = np.zeros(mb * Z + 1, dtype=np.int32)
+    row_ptr[1:] = np.cumsum(np.repeat(deg, Z), dtype=np.int64)
+    r = np.arange(Z)[:, None]
+    cols = []
+    for i in range(mb):
+        j = np.nonzero(base[i] >= 0)[0]  # ascending block columns: ascending columns within a row
+        cols.append((j[None, :] * Z + (r + base[i, j][None, :]) % Z).ravel())
+    return row_ptr, np.concatenate(cols).astype(np.int32)
+
+
+def qc_block_layers(mb: int, Z: int, order=None) -> list:
+    """The block rows as layers: int arrays [i Z, (i+1) Z) for i in `order`
+    (default 0 .. mb-1).  The Z checks of a block row share no variable."""
+    order = range(mb) if order is None else order
+    return [np.arange(int(i) * Z, (int(i) + 1) * Z, dtype=np.int64) for i in order]
+
+
+def qc_random_base(mb: int, nb: int, Z: int, dv: int, seed: int) -> np.ndarray:
+    """A seeded random base matrix: every block column gets dv non-zero blocks in
+    distinct block rows with uniform shifts; the whole matrix is redrawn (the
+    generator continuing) until every block row has at least 2 non-zero blocks."""
+    rng = np.random.RandomState(seed)
+    while True:
+        base = np.full((mb, nb), -1, dtype=np.int64)
+        for j in range(nb):
+            rows = rng.choice(mb, dv, replace=False)
+            base[rows, j] = rng.randint(0, Z, dv)
+        if np.all((base >= 0).sum(axis=1) >= 2):
+            return base
+
+
 def mackay_construction(n: int, k: int, dv: int, dc: int, seed: Optional[int] = None) -> np.ndarray:
     m = n - k
     if dv * n != dc * m:

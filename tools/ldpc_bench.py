@@ -1,13 +1,18 @@
 """LDPC decode kernel timing (diagnostic): HIP events around repeated launches.
 
-usage: python tools/ldpc_bench.py [--batch 65536] [--algo bp,ms,lms] [--n 504] [--seed 3]
-                                  [--max-iter 20] [--no-early-stop] [--snr 3.0] [--valid]
-                                  [--norm 0.75] [--reps 5] [--rounds 3]
+usage: python tools/ldpc_bench.py [--batch 65536] [--algo bp,ms,lms,qclms] [--n 504] [--seed 3]
+                                  [--qc mb,nb,Z,dv,seed] [--max-iter 20] [--no-early-stop]
+                                  [--snr 3.0] [--valid] [--norm 0.75] [--reps 5] [--rounds 3]
 
 Default (no --n): the bench's (504,252) MacKay code (seed 42, degree-1 rows: BP
 only) with the bench's invalid codewords, or --valid for the all-zero codeword.
 --n N: regular_construction(N, 3, 6, seed) with the all-zero codeword, which all
 three algorithms decode (ms and lms need --n: the default code has degree-1 rows).
+--qc mb,nb,Z,dv,seed: the quasi-cyclic code qc_random_base(mb, nb, Z, dv, seed) with
+the all-zero codeword; `qclms` is QCLayeredMSDecoder on the base matrix and `lms`
+the generic layered decoder on the same H (from qc_to_csr, never dense) with the
+same block-row layers.  With both, their bits and iteration counts on the timed
+frames must be equal (asserted).
 --algo takes a comma-separated list; the decoders are timed alternately on the
 same frames, `rounds` times each, and one JSON line per entry gives the median
 and the spread of the per-launch time.  Each entry may carry its own iteration
@@ -17,7 +22,9 @@ import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from polarcode_and_ldpc_amd.channel import AWGNChannel
-from polarcode_and_ldpc_amd.ldpc import BPDecoder, MSDecoder, LayeredMSDecoder, LDPCEncoder, regular_construction
+from polarcode_and_ldpc_amd import _native
+from polarcode_and_ldpc_amd.ldpc import (BPDecoder, MSDecoder, LayeredMSDecoder, LDPCEncoder, QCLayeredMSDecoder,
+                                         qc_block_layers, qc_random_base, qc_to_csr, regular_construction)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=65536)
@@ -29,11 +36,19 @@ ap.add_argument("--no-early-stop", action="store_true")
 ap.add_argument("--norm", type=float, default=0.75, help="min-sum normalisation (ms, lms)")
 ap.add_argument("--n", type=int, default=0, help="regular (3,6) code of this length instead of the bench's code")
 ap.add_argument("--seed", type=int, default=3, help="regular_construction seed (--n)")
+ap.add_argument("--qc", default="", help="mb,nb,Z,dv,seed: a qc_random_base code instead (algos lms, qclms)")
 ap.add_argument("--reps", type=int, default=5, help="launches per timed round")
 ap.add_argument("--rounds", type=int, default=3)
 a = ap.parse_args()
 B = a.batch
-if a.n:
+qc = None
+if a.qc:
+    mb, nb, Z, dv, qseed = (int(x) for x in a.qc.split(","))
+    qc = qc_random_base(mb, nb, Z, dv, qseed)
+    n, k = nb * Z, (nb - mb) * Z
+    H = None
+    cw = None
+elif a.n:
     n, k = a.n, a.n // 2
     H = regular_construction(n, 3, 6, seed=a.seed)
     cw = None
@@ -50,9 +65,28 @@ else:
 es = not a.no_early_stop
 
 
+class GenericOnQc:
+    """The generic layered decoder on the expanded quasi-cyclic H with the block rows as layers."""
+
+    def __init__(self, max_iter):
+        rp, ci = qc_to_csr(qc, Z)
+        self.plan = _native.layered_ldpc_plan(rp, ci, n, qc_block_layers(mb, Z), max_iter, es, a.norm)
+
+    def _check_runnable(self):
+        pass
+
+
 def make(spec):
     name, _, mi = spec.partition(":")
     mi = int(mi) if mi else a.max_iter
+    if qc is not None:
+        if name == "qclms":
+            return QCLayeredMSDecoder(qc, Z, max_iter=mi, normalization=a.norm, early_stop=es)
+        if name == "lms":
+            return GenericOnQc(mi)
+        raise SystemExit("--qc takes --algo lms and qclms only, not %r" % spec)
+    if name == "qclms":
+        raise SystemExit("--algo qclms needs --qc mb,nb,Z,dv,seed")
     if name == "bp":
         return BPDecoder(H, max_iter=mi, early_stop=es)
     if name == "ms":
@@ -63,7 +97,7 @@ def make(spec):
 
 
 specs = a.algo.split(",")
-if not a.n and any(s.partition(":")[0] in ("ms", "lms") for s in specs):
+if not a.n and qc is None and any(s.partition(":")[0] in ("ms", "lms") for s in specs):
     raise SystemExit("the default (504,252) code has degree-1 rows, which min-sum cannot decode: "
                      "give --n N (a regular (3,6) code) with --algo ms / lms")
 decs = [make(s) for s in specs]
@@ -71,13 +105,21 @@ llr = AWGNChannel(a.snr).llr_batch_device(cw, n, B, seed=4242)
 out = torch.empty((B, n), dtype=torch.uint8, device="cuda")
 its = torch.empty((B,), dtype=torch.int32, device="cuda")
 stats = []
-for d in decs:  # warm-up: plan creation, workspace, first launch
+results = {}
+for s, d in zip(specs, decs):  # warm-up: plan creation, workspace, first launch
     d._check_runnable()
     d.plan.decode(llr, out, its)
     torch.cuda.synchronize()
     wrong = (out != 0).any(dim=1) if cw is None else None
     stats.append({"mean_iter": float(its.double().mean()),
                   "frame_errors": int(wrong.sum()) if wrong is not None else None})
+    if qc is not None:
+        results[s] = (out.clone(), its.clone())
+if qc is not None:  # the two decoders are one definition: equal on the timed frames
+    names = {s.partition(":")[0]: s for s in specs if s.partition(":")[2] in ("", str(a.max_iter))}
+    if "lms" in names and "qclms" in names:
+        (b0, i0), (b1, i1) = results[names["lms"]], results[names["qclms"]]
+        assert torch.equal(b0, b1) and torch.equal(i0, i1), "qclms and lms differ on the timed frames"
 times = [[] for _ in decs]
 for _ in range(a.rounds):
     for i, d in enumerate(decs):  # alternated, so drift hits every decoder alike
