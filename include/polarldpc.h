@@ -57,7 +57,9 @@ typedef struct {
                            10 layered min-sum with its state in the workspace,
                            11 quasi-cyclic layered min-sum with its state in LDS,
                            12 quasi-cyclic layered min-sum with its state in the
-                           workspace                                                */
+                           workspace,
+                           13 / 14 the same two with the state in single precision
+                           (PL_LDPC_QC_F32)                                         */
 } pl_plan_info;
 
 /* Polar SC / SCL plan.
@@ -156,7 +158,29 @@ int pl_ldpc_layered_plan_create(int32_t m, int32_t n, const int32_t* row_ptr, co
  *   (pl_plan_info.reserved 11), else in the workspace (12); PL_LMS_GLOBAL=1
  *   forces the workspace.  pl_decode, pl_decode_ws, pl_ldpc_decode_soft,
  *   pl_plan_workspace_bytes, pl_plan_reserve and pl_plan_release work as for a
- *   layered plan. */
+ *   layered plan.
+ *   flags: bit 0 is PL_LDPC_QC_F32, the other bits are ignored.
+ *   PL_LDPC_QC_F32: the same decoder with every value and every operation in
+ *   IEEE binary32 -- the layered definition printed at
+ *   pl_ldpc_layered_plan_create, read in single precision:
+ *     P[v] = (float)llr[v]   round to nearest even for an fp64 input (beyond
+ *                            FLT_MAX: +-inf; 5e-324: 0), an fp32 input as it is
+ *     norm32 = (float)normalization, rounded once on the host
+ *     q[j] = P[v_j] - R[c][j]
+ *     R[c][j] = (prod_{k != j} sign(q[k]) * min_{k != j} |q[k]|) * norm32
+ *     P[v_j] = q[j] + R[c][j]
+ *   each step one rounding (no FMA contraction, no double intermediate),
+ *   subnormals kept (not flushed); NaN, zero and sign rules as in fp64;
+ *   decisions P <= 0 and the early stop as in fp64.  Bits, iteration counts and
+ *   posteriors equal a NumPy float32 restatement bit for bit; they are not the
+ *   fp64 decoder's rounded.  State per frame 4 n + 8 m + 4 mw m bytes (mw meta
+ *   words per check) against 8 n + 16 m + 4 mw m, under the same LDS rules
+ *   (pl_plan_info.reserved 13 in LDS, 14 in the workspace; the workspace unit
+ *   is the single-precision state).  Such a plan takes fp32 LLRs through
+ *   pl_ldpc_decode_f32, and fp64 LLRs through pl_decode, pl_decode_ws and
+ *   pl_ldpc_decode_soft, which round each LLR on load and widen the posteriors
+ *   on store (exact), with no conversion pass. */
+#define PL_LDPC_QC_F32 1
 int pl_ldpc_qc_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift /* [mb*nb] row-major */,
                            const int32_t* layer_order /* [mb] or NULL */, int32_t max_iter, int32_t early_stop,
                            double normalization, int32_t flags, pl_plan** out);
@@ -203,6 +227,17 @@ int pl_decode_ws(pl_plan* plan, const double* llr_dev, int64_t batch, int64_t ld
 int pl_ldpc_decode_soft(pl_plan* plan, const double* llr_dev, int64_t batch, int64_t ld, uint8_t* bits_dev,
                         int32_t* iters_dev, double* post_dev, int64_t ld_post, void* stream);
 
+/* Decode of a quasi-cyclic plan created with PL_LDPC_QC_F32 from fp32 LLRs:
+ * llr_dev fp32 [batch][ld]; post_dev fp32 [batch][ld_post], ld_post >= n, or
+ * NULL for no posterior output; workspace_dev NULL: the plan's per-stream
+ * workspace as pl_decode, else a caller-owned one of workspace_bytes as
+ * pl_decode_ws (no allocation).  The other arguments as pl_decode.
+ * PL_EUNSUPPORTED for every plan without the flag. */
+int pl_ldpc_decode_f32(pl_plan* plan, const float* llr_dev, int64_t batch, int64_t ld, uint8_t* bits_dev,
+                       int32_t* iters_dev, float* post_dev /* may be NULL */, int64_t ld_post,
+                       void* workspace_dev /* NULL: the plan's per-stream workspace */, int64_t workspace_bytes,
+                       void* stream);
+
 /* Pre-allocate `stream`'s workspace for batches up to max_batch, so that
  * pl_decode on that stream never allocates (max_batch == 0: pl_plan_release).
  * If the device cannot hold the full-speed size, the largest halving of at
@@ -232,7 +267,7 @@ int pl_plan_destroy(pl_plan* plan);
 const char* pl_last_error(void);
 
 /* Calls that touch a plan's device memory -- pl_decode, pl_decode_ws,
- * pl_ldpc_decode_soft, pl_plan_reserve, pl_plan_release, pl_polar_plan_set_crc, pl_polar_encode,
+ * pl_ldpc_decode_soft, pl_ldpc_decode_f32, pl_plan_reserve, pl_plan_release, pl_polar_plan_set_crc, pl_polar_encode,
  * pl_debug_polar_stamps -- must run with the plan's device current (the device
  * current at plan creation); otherwise they return PL_EINVAL and do nothing.
  * pl_plan_get_info, pl_plan_workspace_bytes and pl_plan_workspace_stats read
@@ -338,7 +373,7 @@ int pl_debug_ldpc_layered_plan_probe(int32_t m, int32_t n, const int32_t* row_pt
  * table_len / digest: the layer stream (per layer the block row, its degree and
  * its (block column, shift) pairs). */
 typedef struct {
-    int32_t kernel;      /* 11 or 12, as pl_plan_info.reserved */
+    int32_t kernel;      /* 11 or 12 (13 or 14 with PL_LDPC_QC_F32), as pl_plan_info.reserved */
     int32_t z, mb, nb, maxdc, dcap, mw, fpw, fpb, threads, lds_bytes, use_global;
     int64_t state_bytes;
     int64_t table_len;
@@ -347,6 +382,13 @@ typedef struct {
 int pl_debug_ldpc_qc_plan_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift, const int32_t* layer_order,
                                 int32_t max_iter, int32_t early_stop, double normalization, int32_t lms_global,
                                 pl_ldpc_qc_plan_probe* out);
+/* The same with pl_ldpc_qc_plan_create's flags (PL_LDPC_QC_F32: kernel 13 or 14,
+ * state_bytes and lds_bytes of the single-precision layout; the layer stream,
+ * table_len and digest do not depend on the flags).  flags 0: the call above. */
+int pl_debug_ldpc_qc_plan_probe_flags(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                      const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
+                                      double normalization, int32_t lms_global, int32_t flags,
+                                      pl_ldpc_qc_plan_probe* out);
 
 /* ---- Monte-Carlo frame source (replaces src/channel/awgn.py:91-112 and the
  *      message/encode loop of benchmarks/ber_simulation.py:167-177) ---------- */

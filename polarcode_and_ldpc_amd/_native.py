@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("PL_LIB_PATH", os.path.join(_HERE, "_lib", "libpolarld
 
 PL_OK, PL_EINVAL, PL_ENOMEM, PL_EHIP, PL_EUNSUPPORTED = 0, -1, -2, -3, -4
 PL_LDPC_BP, PL_LDPC_MS, PL_LDPC_LMS = 0, 1, 2
+PL_LDPC_QC_F32 = 1  # pl_ldpc_qc_plan_create flag: state and arithmetic in single precision
 
 EXPORTS = (
     "pl_polar_plan_create", "pl_ldpc_plan_create", "pl_decode", "pl_plan_reserve", "pl_plan_get_info",
@@ -27,7 +28,7 @@ EXPORTS = (
     "pl_plan_release", "pl_plan_workspace_stats", "pl_debug_set_plan_device", "pl_debug_polar_fpw",
     "pl_debug_polar_flagged", "pl_polar_plan_small_batch", "pl_ldpc_layered_plan_create", "pl_ldpc_decode_soft",
     "pl_debug_ldpc_plan_probe", "pl_debug_ldpc_layered_plan_probe", "pl_ldpc_qc_plan_create",
-    "pl_debug_ldpc_qc_plan_probe",
+    "pl_debug_ldpc_qc_plan_probe", "pl_ldpc_decode_f32", "pl_debug_ldpc_qc_plan_probe_flags",
 )
 
 
@@ -78,7 +79,10 @@ def _load(path=LIB_PATH):
                                                    ctypes.POINTER(LdpcLayeredPlanProbe)]
     L.pl_ldpc_qc_plan_create.argtypes = [I32, I32, I32, P, P, I32, I32, D, I32, PP]
     L.pl_debug_ldpc_qc_plan_probe.argtypes = [I32, I32, I32, P, P, I32, I32, D, I32, ctypes.POINTER(LdpcQcPlanProbe)]
+    L.pl_debug_ldpc_qc_plan_probe_flags.argtypes = [I32, I32, I32, P, P, I32, I32, D, I32, I32,
+                                                    ctypes.POINTER(LdpcQcPlanProbe)]
     L.pl_ldpc_decode_soft.argtypes = [P, P, I64, I64, P, P, P, I64, P]
+    L.pl_ldpc_decode_f32.argtypes = [P, P, I64, I64, P, P, P, I64, P, I64, P]
     L.pl_decode.argtypes = [P, P, I64, I64, P, P, P]
     L.pl_plan_reserve.argtypes = [P, I64, P]
     L.pl_decode_ws.argtypes = [P, P, I64, I64, P, P, P, I64, P]
@@ -177,6 +181,8 @@ class Plan:
         info = PlanInfo()
         check(lib.pl_plan_get_info(self._h, ctypes.byref(info)), "pl_plan_get_info")
         self.info = info
+        # a quasi-cyclic plan created with PL_LDPC_QC_F32 (it also takes fp32 llr / post); fixed at creation
+        self.f32 = info.reserved in (13, 14)
 
     @property
     def handle(self):
@@ -211,7 +217,12 @@ class Plan:
         # the kernels write bits at row pitch n_out and iters densely; llr rows
         # may carry any pitch >= n_in but unit inner stride
         assert isinstance(llr, torch.Tensor) and llr.is_cuda, "llr must be a device tensor"
-        assert llr.dtype == torch.float64 and llr.dim() == 2 and llr.stride(1) == 1 and llr.shape[1] >= self.info.n_in
+        if llr.dtype == torch.float32:
+            assert self.f32, "fp32 llr: quasi-cyclic plans created with PL_LDPC_QC_F32 only"
+            assert llr.dim() == 2 and llr.stride(1) == 1 and llr.shape[1] >= self.info.n_in
+        else:
+            assert llr.dtype == torch.float64 and llr.dim() == 2 and llr.stride(1) == 1 \
+                and llr.shape[1] >= self.info.n_in
         assert bits.is_cuda and bits.dtype == torch.uint8 and bits.shape == (llr.shape[0], self.info.n_out)
         assert bits.is_contiguous(), "bits must be contiguous [B, n_out] (row pitch n_out)"
         if iters is not None:
@@ -221,12 +232,20 @@ class Plan:
     def decode(self, llr: "torch.Tensor", bits: "torch.Tensor", iters: "torch.Tensor | None" = None, stream=None,
                ws: "torch.Tensor | None" = None):
         """llr fp64 [B, >=n_in] device, bits uint8 [B, n_out] contiguous, iters int32 [B]
-        or None; ws: optional caller-owned uint8 device workspace (pl_decode_ws)."""
+        or None; ws: optional caller-owned uint8 device workspace (pl_decode_ws).
+        A PL_LDPC_QC_F32 plan also takes fp32 llr (pl_ldpc_decode_f32)."""
         self._check(llr, bits, iters)
         B = llr.shape[0]
         it = ctypes.c_void_p(iters.data_ptr()) if iters is not None else None
         st = ctypes.c_void_p(_stream(stream))
-        if ws is None:
+        if llr.dtype == torch.float32:
+            assert ws is None or (ws.is_cuda and ws.is_contiguous())
+            check(lib.pl_ldpc_decode_f32(self._h, ctypes.c_void_p(llr.data_ptr()), B, _ld(llr),
+                                         ctypes.c_void_p(bits.data_ptr()), it, None, 0,
+                                         None if ws is None else ctypes.c_void_p(ws.data_ptr()),
+                                         0 if ws is None else ws.numel() * ws.element_size(), st),
+                  "pl_ldpc_decode_f32")
+        elif ws is None:
             check(lib.pl_decode(self._h, ctypes.c_void_p(llr.data_ptr()), B, _ld(llr),
                                 ctypes.c_void_p(bits.data_ptr()), it, st), "pl_decode")
         else:
@@ -239,12 +258,20 @@ class Plan:
                     post: "torch.Tensor", stream=None):
         """decode() of a layered min-sum plan that also writes the posterior LLRs:
         post fp64 [B, >=n] device with unit inner stride (pl_ldpc_decode_soft).
-        Any other plan kind raises ValueError."""
+        Any other plan kind raises ValueError.  A PL_LDPC_QC_F32 plan also takes
+        llr and post both fp32 (pl_ldpc_decode_f32)."""
         self._check(llr, bits, iters)
-        assert post.is_cuda and post.dtype == torch.float64 and post.dim() == 2 and post.stride(1) == 1 \
+        assert post.is_cuda and post.dtype == llr.dtype and post.dim() == 2 and post.stride(1) == 1 \
             and post.shape[0] == llr.shape[0] and post.shape[1] >= self.info.n_in, \
-            "post must be a float64 [B, >=n] device tensor with unit inner stride"
+            "post must be a [B, >=n] device tensor of llr's dtype (float64; float32 on a PL_LDPC_QC_F32 plan) " \
+            "with unit inner stride"
         it = ctypes.c_void_p(iters.data_ptr()) if iters is not None else None
+        if llr.dtype == torch.float32:
+            check(lib.pl_ldpc_decode_f32(self._h, ctypes.c_void_p(llr.data_ptr()), llr.shape[0], _ld(llr),
+                                         ctypes.c_void_p(bits.data_ptr()), it, ctypes.c_void_p(post.data_ptr()),
+                                         _ld(post), None, 0, ctypes.c_void_p(_stream(stream))),
+                  "pl_ldpc_decode_f32")
+            return
         check(lib.pl_ldpc_decode_soft(self._h, ctypes.c_void_p(llr.data_ptr()), llr.shape[0], _ld(llr),
                                       ctypes.c_void_p(bits.data_ptr()), it, ctypes.c_void_p(post.data_ptr()),
                                       _ld(post), ctypes.c_void_p(_stream(stream))), "pl_ldpc_decode_soft")
@@ -321,9 +348,10 @@ def layered_ldpc_plan(row_ptr: np.ndarray, col_idx: np.ndarray, n: int, layers, 
 
 
 def qc_ldpc_plan(base: np.ndarray, Z: int, layer_order, max_iter: int, early_stop: bool,
-                 normalization: float = 1.0) -> Plan:
+                 normalization: float = 1.0, flags: int = 0) -> Plan:
     """Quasi-cyclic layered min-sum plan (pl_ldpc_qc_plan_create); base: int [mb, nb]
-    shifts (-1: zero block); layer_order: a permutation of the block rows or None."""
+    shifts (-1: zero block); layer_order: a permutation of the block rows or None;
+    flags: 0 or PL_LDPC_QC_F32."""
     sh = np.ascontiguousarray(base, dtype=np.int32)
     assert sh.ndim == 2, "base must be [mb, nb]"
     lo = None if layer_order is None else np.ascontiguousarray(layer_order, dtype=np.int32).ravel()
@@ -332,7 +360,7 @@ def qc_ldpc_plan(base: np.ndarray, Z: int, layer_order, max_iter: int, early_sto
     h = ctypes.c_void_p()
     check(lib.pl_ldpc_qc_plan_create(sh.shape[0], sh.shape[1], int(Z), sh.ctypes.data_as(ctypes.c_void_p),
                                      None if lo is None else lo.ctypes.data_as(ctypes.c_void_p), int(max_iter),
-                                     int(bool(early_stop)), float(normalization), 0, ctypes.byref(h)),
+                                     int(bool(early_stop)), float(normalization), int(flags), ctypes.byref(h)),
           "pl_ldpc_qc_plan_create")
     return Plan(h)
 

@@ -71,6 +71,7 @@ struct pl_plan {
     // quasi-cyclic layered min-sum (ldpc_qc_layered.hip): a layered plan (lms.n, lms.m set) whose
     // kernel geometry is qcg and whose table buffer is the layer stream
     bool qc = false;
+    bool qc_f32 = false;  // created with PL_LDPC_QC_F32: state and arithmetic in single precision
     pl::QcGeom qcg{};
     // workspace: bytes per unit (polar: one resident wave; LDPC global: one
     // frame), one buffer per stream (plans are shared across host threads that
@@ -379,22 +380,24 @@ extern "C" int pl_ldpc_layered_plan_create(int32_t m, int32_t n, const int32_t* 
 extern "C" int pl_ldpc_qc_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
                                       const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
                                       double normalization, int32_t flags, pl_plan** out) {
-    (void)flags;
     if (!out) return fail(PL_EINVAL, "out is NULL");
     *out = nullptr;
     // every argument check (ldpc_plan.cpp) comes before the first device call
     pl::QcHostPlan hp;
+    pl::LdpcPlanOptions opt = ldpc_env_options();
+    if (flags & PL_LDPC_QC_F32) opt.qc_state_elem = 4;  // the other bits are ignored
     const pl::PlanStatus st = pl::qc_plan_build(mb, nb, z, shift, layer_order, max_iter, early_stop, normalization,
-                                                ldpc_env_options(), &hp);
+                                                opt, &hp);
     if (st.code) return fail(st.code, st.msg);
     pl_plan* p;
     if (int rc = ldpc_plan_upload(hp.tables, &p)) return rc;
     p->layered = true;
     p->qc = true;
     p->qcg = hp.geom;
+    p->qc_f32 = hp.f32;
     p->lg.n = p->lms.n = hp.geom.n;
     p->lg.m = p->lms.m = hp.geom.m;
-    const hipError_t e = pl::qc_prepare(p->qcg);
+    const hipError_t e = pl::qc_prepare(p->qcg, p->qc_f32);
     if (e != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "hipFuncSetAttribute"); }
     p->ws_unit = p->qcg.use_global ? (size_t)p->qcg.state_bytes : 0;
     *out = p;
@@ -438,19 +441,29 @@ extern "C" int pl_debug_ldpc_layered_plan_probe(int32_t m, int32_t n, const int3
     return PL_OK;
 }
 
-extern "C" int pl_debug_ldpc_qc_plan_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
-                                           const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
-                                           double normalization, int32_t lms_global, pl_ldpc_qc_plan_probe* out) {
+extern "C" int pl_debug_ldpc_qc_plan_probe_flags(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                                 const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
+                                                 double normalization, int32_t lms_global, int32_t flags,
+                                                 pl_ldpc_qc_plan_probe* out) {
     if (!out) return fail(PL_EINVAL, "out is NULL");
     pl::QcHostPlan hp;
+    pl::LdpcPlanOptions opt = ldpc_options(0, 0, lms_global);
+    if (flags & PL_LDPC_QC_F32) opt.qc_state_elem = 4;
     const pl::PlanStatus st = pl::qc_plan_build(mb, nb, z, shift, layer_order, max_iter, early_stop, normalization,
-                                                ldpc_options(0, 0, lms_global), &hp);
+                                                opt, &hp);
     if (st.code) return fail(st.code, st.msg);
     const pl::QcGeom& g = hp.geom;
-    *out = pl_ldpc_qc_plan_probe{pl::qc_kernel_code(g), g.z, g.mb, g.nb, g.maxdc, g.dcap, g.mw, g.fpw, g.fpb,
+    *out = pl_ldpc_qc_plan_probe{pl::qc_kernel_code(g, hp.f32), g.z, g.mb, g.nb, g.maxdc, g.dcap, g.mw, g.fpw, g.fpb,
                                  g.threads, g.lds_bytes, g.use_global, g.state_bytes, (int64_t)hp.tables.size(),
                                  pl::plan_tables_digest(hp.tables)};
     return PL_OK;
+}
+
+extern "C" int pl_debug_ldpc_qc_plan_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                           const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
+                                           double normalization, int32_t lms_global, pl_ldpc_qc_plan_probe* out) {
+    return pl_debug_ldpc_qc_plan_probe_flags(mb, nb, z, shift, layer_order, max_iter, early_stop, normalization,
+                                             lms_global, 0, out);
 }
 
 // Polar workspace layout for a grid of `grid` resident wavefronts: a list
@@ -489,11 +502,13 @@ struct DecodeDiag {
     uint8_t* flagged = nullptr;
 };
 
-// Layered min-sum decode; post (fp64 [batch][ld_post]) may be null.  LDS-resident
+// Layered min-sum decode; post ([batch][ld_post]) may be null.  LDS-resident
 // state: launches below the grid limit; workspace-resident: chunks of the frames
-// the workspace holds (one state slice per frame of a chunk).
-static int lms_decode_impl(pl_plan* p, const double* llr, int64_t batch, int64_t ld, uint8_t* bits, int32_t* iters,
-                           double* post, int64_t ld_post, void* ws, size_t ws_bytes, hipStream_t s) {
+// the workspace holds (one state slice per frame of a chunk).  IO: double, or
+// float on a quasi-cyclic plan made with PL_LDPC_QC_F32 (pl_ldpc_decode_f32 checks that).
+template <typename IO>
+static int lms_decode_impl(pl_plan* p, const IO* llr, int64_t batch, int64_t ld, uint8_t* bits, int32_t* iters,
+                           IO* post, int64_t ld_post, void* ws, size_t ws_bytes, hipStream_t s) {
     if (p->ws_unit > 0 && (ws == nullptr || ws_bytes < p->ws_unit))
         return fail(PL_EINVAL, "workspace smaller than one unit (pl_plan_workspace_bytes)");
     const int64_t step = p->ws_unit > 0 ? std::min<int64_t>(p->ldpc_chunk, (int64_t)(ws_bytes / p->ws_unit))
@@ -502,11 +517,16 @@ static int lms_decode_impl(pl_plan* p, const double* llr, int64_t batch, int64_t
         const int64_t nb = std::min<int64_t>(step, batch - b0);
         uint8_t* const bo = bits + b0 * p->lms.n;
         int32_t* const io = iters ? iters + b0 : nullptr;
-        double* const po = post ? post + b0 * ld_post : nullptr;
-        hipError_t e = p->qc ? pl::qc_launch(p->qcg, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
-                                             (unsigned char*)ws, s)
-                             : pl::lms_launch(p->lms, p->lmsd, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
-                                              (unsigned char*)ws, s);
+        IO* const po = post ? post + b0 * ld_post : nullptr;
+        hipError_t e;
+        if constexpr (sizeof(IO) == sizeof(double)) {
+            e = p->qc ? pl::qc_launch(p->qcg, p->qc_f32, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
+                                      (unsigned char*)ws, s)
+                      : pl::lms_launch(p->lms, p->lmsd, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
+                                       (unsigned char*)ws, s);
+        } else {
+            e = pl::qc_launch(p->qcg, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb, (unsigned char*)ws, s);
+        }
         if (e != hipSuccess) return hipfail(e, "layered ldpc decode launch");
     }
     return PL_OK;
@@ -518,7 +538,7 @@ static int decode_impl(pl_plan* p, const double* llr, int64_t batch, int64_t ld,
                        void* ws, size_t ws_bytes, hipStream_t s, bool zero_masks = false,
                        const DecodeDiag& dg = DecodeDiag()) {
     unsigned long long* const stamps = dg.stamps;
-    if (p->layered) return lms_decode_impl(p, llr, batch, ld, bits, iters, nullptr, 0, ws, ws_bytes, s);
+    if (p->layered) return lms_decode_impl<double>(p, llr, batch, ld, bits, iters, nullptr, 0, ws, ws_bytes, s);
     const size_t wmin = ws_min(p);
     if (wmin > 0 && (ws == nullptr || ws_bytes < wmin))
         return fail(PL_EINVAL, "workspace smaller than one unit (pl_plan_workspace_bytes)");
@@ -776,6 +796,29 @@ extern "C" int pl_ldpc_decode_soft(pl_plan* p, const double* llr, int64_t batch,
     return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, w->ptr, w->bytes, s);
 }
 
+extern "C" int pl_ldpc_decode_f32(pl_plan* p, const float* llr, int64_t batch, int64_t ld, uint8_t* bits,
+                                  int32_t* iters, float* post, int64_t ld_post, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+    if (!p) return fail(PL_EINVAL, "plan is NULL");
+    if (!p->qc || !p->qc_f32)
+        return fail(PL_EUNSUPPORTED, "fp32 LLRs: quasi-cyclic plans created with PL_LDPC_QC_F32 only");
+    int rc = check_decode_args(p, batch, ld, llr, bits);
+    if (rc) return rc;
+    if (post && ld_post < p->lms.n) return fail(PL_EINVAL, "ld_post < n");
+    if (workspace && workspace_bytes < 0) return fail(PL_EINVAL, "workspace_bytes < 0");
+    if (batch == 0) return PL_OK;
+    if ((rc = check_device(p))) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (workspace)
+        return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, workspace, (size_t)workspace_bytes, s);
+    const size_t need = ws_need(p, batch);
+    if (!need) return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, nullptr, 0, s);
+    std::shared_ptr<Workspace> w = stream_entry(p, s);
+    std::lock_guard<std::mutex> lk(w->mu);
+    if ((rc = grow_ws(p, w.get(), s, need, false))) return rc;
+    return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, w->ptr, w->bytes, s);
+}
+
 extern "C" int pl_debug_polar_stamps(pl_plan* p, const double* llr, int64_t batch, int64_t ld, uint8_t* bits,
                                      unsigned long long* stamps_dev, void* stream) {
     if (!p || p->kind != 0 || !stamps_dev) return fail(PL_EINVAL, "polar plan and stamp buffer required");
@@ -927,9 +970,9 @@ extern "C" int pl_plan_get_info(const pl_plan* p, pl_plan_info* info) {
         info->kind = 1; info->n_in = p->lms.n; info->n_out = p->lms.n; info->list_size = 0;
         info->lds_bytes = p->lms.lds_bytes; info->fused_top = 0; info->frames_per_block = p->lms.fpb;
         info->reserved = pl::lms_kernel_code(p->lms);  // layered min-sum: 9 state in LDS, 10 in the workspace
-        if (p->qc) {  // quasi-cyclic layered min-sum: 11 state in LDS, 12 in the workspace
+        if (p->qc) {  // quasi-cyclic layered min-sum: 11 state in LDS, 12 in the workspace; fp32 state: 13, 14
             info->lds_bytes = p->qcg.lds_bytes; info->frames_per_block = p->qcg.fpw * p->qcg.fpb;
-            info->reserved = pl::qc_kernel_code(p->qcg);
+            info->reserved = pl::qc_kernel_code(p->qcg, p->qc_f32);
         }
     } else {
         info->kind = 1; info->n_in = p->lg.n; info->n_out = p->lg.n; info->list_size = 0;

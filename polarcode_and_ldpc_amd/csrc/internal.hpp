@@ -135,9 +135,13 @@ hipError_t lms_launch(const LmsGeom& g, const LmsDev& d, const double* llr, int6
                       double* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
 
 // ---- quasi-cyclic layered min-sum (ldpc_qc_layered.hip); QcGeom: ldpc_plan.hpp ----
-hipError_t qc_prepare(const QcGeom& g);
+// f32: a single-precision plan (QcHostPlan::f32): the float instances, which take fp64 or fp32 llr / post
+hipError_t qc_prepare(const QcGeom& g, bool f32);
 // tab: the plan's layer stream (device); the other arguments as lms_launch
-hipError_t qc_launch(const QcGeom& g, const int32_t* tab, const double* llr, int64_t ld, uint8_t* bits, int32_t* iters,
-                     double* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
+hipError_t qc_launch(const QcGeom& g, bool f32, const int32_t* tab, const double* llr, int64_t ld, uint8_t* bits,
+                     int32_t* iters, double* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
+// fp32 llr and post: single-precision plans only (the caller checks)
+hipError_t qc_launch(const QcGeom& g, const int32_t* tab, const float* llr, int64_t ld, uint8_t* bits, int32_t* iters,
+                     float* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
 
 }  // namespace pl

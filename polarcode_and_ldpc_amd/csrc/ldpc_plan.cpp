@@ -473,10 +473,18 @@ PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int3
     lms_geom(&lg, opt.lms_global);
     QcGeom& g = out->geom;
     g = QcGeom{};
+    out->f32 = false;
     g.mb = mb; g.nb = nb; g.z = z; g.m = lg.m; g.n = lg.n; g.max_iter = max_iter; g.early_stop = early_stop ? 1 : 0;
     g.maxdc = maxdc; g.norm = norm; g.mw = lg.mw;
     g.dcap = maxdc <= 8 ? 8 : maxdc <= 16 ? 16 : maxdc <= kQcDcapMax ? 32 : 0;
     g.state_bytes = lg.state_bytes; g.off_mm = lg.off_mm; g.off_meta = lg.off_meta;
+    if (opt.qc_state_elem == 4) {  // the same arrays with 4-byte P and minima; the rules below see the new sizes
+        out->f32 = true;
+        g.norm = (double)(float)norm;  // rounded once, here; the kernel's (float)g.norm is exact
+        g.off_mm = (int64_t)ldpc_align16((size_t)4 * g.n);
+        g.off_meta = g.off_mm + (int64_t)8 * g.m;
+        g.state_bytes = (int64_t)ldpc_align16((size_t)g.off_meta + (size_t)4 * g.m * g.mw);
+    }
     g.subwave = z <= 64 ? 1 : 0;
     if (g.subwave) {
         // fpw frames side by side in a wavefront's lanes; the LDS bound of lms_geom's WAVE case, per wavefront

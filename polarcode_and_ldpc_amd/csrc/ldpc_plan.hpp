@@ -151,6 +151,7 @@ struct LdpcPlanOptions {
     int kernel = kLdpcKernelDefault;
     int bp_fpg = 0;           // PL_BP_FPG: frames per workgroup of ldpc_bp_grp_kernel, 1 or 2; 0: the variant's default
     bool lms_global = false;  // PL_LMS_GLOBAL: layered state in the workspace
+    int qc_state_elem = 8;    // qc_plan_build: bytes of a state element, 8 (fp64) or 4 (PL_LDPC_QC_F32)
 };
 
 // Element offsets of LdpcDev's members in LdpcHostPlan::tables.
@@ -192,10 +193,12 @@ PlanStatus lms_plan_build(int m, int n, const int32_t* row_ptr, const int32_t* c
 
 // ---- quasi-cyclic layered min-sum (ldpc_qc_layered.hip) ----
 // H is mb x nb blocks of z x z, each zero or a cyclically shifted identity; a
-// block row is a layer.  State layout per frame: lms_geom's.
+// block row is a layer.  State layout per frame: lms_geom's; with f32 the same
+// arrays in single precision: P[n] f32, at off_mm = align16(4 n) [m] float2, at
+// off_meta = off_mm + 8 m the same [m][mw] u32, state_bytes = align16(off_meta + 4 m mw).
 struct QcGeom {
     int mb, nb, z, m, n, max_iter, early_stop, maxdc;
-    double norm;
+    double norm;     // a single-precision plan: (float)normalization, rounded by the planner (exact as a float)
     int mw;          // meta words per check, as LmsGeom::mw
     int dcap;        // inputs of a check kept in registers: 8, 16 or 32 (>= maxdc); 0: two-pass form
     int subwave;     // 1 (z <= 64): fpw frames share a wavefront; 0: one workgroup per frame
@@ -207,9 +210,10 @@ struct QcGeom {
 };
 constexpr int kQcMaxZ = 1024;
 constexpr int kQcDcapMax = 32;  // largest register-resident instance of ldpc_qc_kernel
-inline int qc_kernel_code(const QcGeom& g) { return g.use_global ? 12 : 11; }
+inline int qc_kernel_code(const QcGeom& g, bool f32 = false) { return (g.use_global ? 12 : 11) + (f32 ? 2 : 0); }
 struct QcHostPlan {
     QcGeom geom{};
+    bool f32 = false;  // state and arithmetic in binary32: the float instances of ldpc_qc_kernel
     // per layer, in layer order: block row, its degree d, then d (block column, shift) pairs by
     // ascending block column -- a stream the kernel walks front to back, 2 + 2 d words a layer
     std::vector<int32_t> tables;

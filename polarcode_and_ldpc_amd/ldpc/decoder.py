@@ -206,6 +206,19 @@ class LayeredMSDecoder(_LdpcBase):
                 f"layers={len(self.layers)})")
 
 
+def _qc_state_dtype(dtype):
+    """np.float64 or np.float32 from a NumPy / torch dtype or its name; anything else: ValueError."""
+    if isinstance(dtype, torch.dtype):
+        dtype = {torch.float64: np.float64, torch.float32: np.float32}.get(dtype, dtype)
+    try:
+        name = None if dtype is None else np.dtype(dtype).name
+    except TypeError:
+        name = None
+    if name not in ("float64", "float32"):
+        raise ValueError("QCLayeredMSDecoder: dtype must be float64 or float32, not %r" % (dtype,))
+    return np.float64 if name == "float64" else np.float32
+
+
 class QCLayeredMSDecoder(LayeredMSDecoder):
     """LayeredMSDecoder for a quasi-cyclic code given by its base matrix
     (ldpc_qc_layered.hip).  `base`: int [mb, nb], -1 a zero Z x Z block, s in
@@ -213,11 +226,22 @@ class QCLayeredMSDecoder(LayeredMSDecoder):
     the block rows, visited in `layer_order` (default 0 .. mb-1).  By definition
     equal, bit for bit, to LayeredMSDecoder(qc_expand(base, Z),
     layers=qc_block_layers(mb, Z, layer_order)); H is never expanded unless `.H`
-    is read."""
+    is read.
+
+    `dtype`: np.float64 (default) or np.float32 (also torch.float32, "float32").
+    A float32 decoder is the same definition with every value and operation in
+    IEEE binary32 (include/polarldpc.h, PL_LDPC_QC_F32): half the state, and
+    fp32 or fp64 device LLRs are read as they are, with no conversion pass on
+    the input.  Its results equal a NumPy float32 restatement bit for bit; they
+    are not the float64 decoder's rounded.  Posteriors come back as float32;
+    for fp64 device LLRs with return_llr the kernel writes them widened to an
+    fp64 [B, n] buffer that is then narrowed (exact), one extra pass and three
+    times the posterior bytes -- pass fp32 LLRs where the posteriors matter."""
 
     def __init__(self, base: np.ndarray, Z: int, max_iter: int = 50, normalization: float = 1.0,
-                 early_stop: bool = True, layer_order=None):
+                 early_stop: bool = True, layer_order=None, dtype=np.float64):
         self._algo = _native.PL_LDPC_LMS
+        self.dtype = _qc_state_dtype(dtype)
         self.base = np.array(base, dtype=np.int64)
         assert self.base.ndim == 2, "base must be [mb, nb]"
         self.Z = int(Z)
@@ -246,9 +270,73 @@ class QCLayeredMSDecoder(LayeredMSDecoder):
     def plan(self):
         if self._plan is None:
             self._plan = _native.qc_ldpc_plan(self.base, self.Z, self.layer_order, self.max_iter, self.early_stop,
-                                              self.normalization)
+                                              self.normalization,
+                                              _native.PL_LDPC_QC_F32 if self.dtype == np.float32 else 0)
         return self._plan
+
+    def _run_soft(self, llr, out=None):
+        if self.dtype != np.float32:
+            return super()._run_soft(llr, out)
+        # llr fp32 or fp64 [B, >=n]; the posteriors are float32 (the state's type)
+        self._check_runnable()
+        B = llr.shape[0]
+        if out is None:
+            out = torch.empty((B, self.n), dtype=torch.uint8, device=llr.device)
+        iters = torch.empty((B,), dtype=torch.int32, device=llr.device)
+        post = torch.empty((B, self.n), dtype=torch.float32, device=llr.device)
+        if B > 0 and llr.dtype == torch.float32:
+            self.plan.decode_soft(llr, out, iters, post)
+        elif B > 0:  # fp64 in: the fp64-I/O instance widens the float32 posteriors, which rounds back exactly
+            wide = torch.empty((B, self.n), dtype=torch.float64, device=llr.device)
+            self.plan.decode_soft(llr, out, iters, wide)
+            post.copy_(wide)
+        return out, iters, post
+
+    def decode_batch(self, llr, out: Optional[torch.Tensor] = None, return_iterations: bool = False,
+                     return_llr: bool = False):
+        """As LayeredMSDecoder.decode_batch.  On a float32 decoder a CUDA float32
+        or float64 tensor (unit inner stride, any row pitch) is decoded in place,
+        any other CUDA float dtype is converted with .to(torch.float32), NumPy
+        input with astype(np.float32), and return_llr gives float32 posteriors
+        (from fp64 LLRs through an fp64 buffer and one narrowing copy: the class
+        docstring)."""
+        if self.dtype != np.float32:
+            return super().decode_batch(llr, out, return_iterations, return_llr)
+
+        def pick(bits, its, post):
+            r = (bits,) + ((its,) if return_iterations else ()) + ((post,) if return_llr else ())
+            return r if len(r) > 1 else bits
+
+        if isinstance(llr, torch.Tensor) and llr.is_cuda:
+            assert llr.dim() == 2 and llr.shape[1] == self.n, "LLR length must be %d" % self.n
+            if llr.dtype not in (torch.float32, torch.float64):
+                llr = llr.to(torch.float32)
+            if llr.stride(1) != 1:
+                llr = llr.contiguous()
+            if return_llr:
+                return pick(*self._run_soft(llr, out))
+            bits, its = self._run(llr, out)
+            return pick(bits, its, None)
+        with np.errstate(all="ignore"):  # beyond FLT_MAX: +-inf, by definition
+            a = np.asarray(llr.cpu().numpy() if isinstance(llr, torch.Tensor) else llr).astype(np.float32)
+        assert a.ndim == 2 and a.shape[1] == self.n, "LLR length must be %d" % self.n
+        if a.shape[0] == 0:
+            self._check_runnable()
+            bits = np.zeros((0, self.n), dtype=np.int64) if out is None else out
+            return pick(bits, np.zeros(0, dtype=np.int64), np.zeros((0, self.n), dtype=np.float32))
+        _native.require_gpu()
+        dev = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        if return_llr:
+            bits, its, post = self._run_soft(dev)
+            post = post.cpu().numpy()
+        else:
+            (bits, its), post = self._run(dev), None
+        b = bits.cpu().numpy().astype(np.int64)
+        if out is not None:
+            out[...] = b
+            b = out
+        return pick(b, its.cpu().numpy().astype(np.int64), post)
 
     def __repr__(self) -> str:
         return (f"QCLayeredMSDecoder(n={self.n}, m={self.m}, Z={self.Z}, max_iter={self.max_iter}, "
-                f"norm={self.normalization})")
+                f"norm={self.normalization}" + (", dtype=float32)" if self.dtype == np.float32 else ")"))

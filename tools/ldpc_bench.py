@@ -1,6 +1,6 @@
 """LDPC decode kernel timing (diagnostic): HIP events around repeated launches.
 
-usage: python tools/ldpc_bench.py [--batch 65536] [--algo bp,ms,lms,qclms] [--n 504] [--seed 3]
+usage: python tools/ldpc_bench.py [--batch 65536] [--algo bp,ms,lms,qclms,qclms32] [--n 504] [--seed 3]
                                   [--qc mb,nb,Z,dv,seed] [--max-iter 20] [--no-early-stop]
                                   [--snr 3.0] [--valid] [--norm 0.75] [--reps 5] [--rounds 3]
 
@@ -12,7 +12,10 @@ three algorithms decode (ms and lms need --n: the default code has degree-1 rows
 the all-zero codeword; `qclms` is QCLayeredMSDecoder on the base matrix and `lms`
 the generic layered decoder on the same H (from qc_to_csr, never dense) with the
 same block-row layers.  With both, their bits and iteration counts on the timed
-frames must be equal (asserted).
+frames must be equal (asserted).  `qclms32` is QCLayeredMSDecoder(dtype=float32)
+on the same device frames, cast once to fp32 outside the timed region; it is
+another decoder (every operation in binary32), so its results are reported, not
+compared: `frames_differ_from_qclms` counts the frames whose bits differ.
 --algo takes a comma-separated list; the decoders are timed alternately on the
 same frames, `rounds` times each, and one JSON line per entry gives the median
 and the spread of the per-launch time.  Each entry may carry its own iteration
@@ -82,11 +85,13 @@ def make(spec):
     if qc is not None:
         if name == "qclms":
             return QCLayeredMSDecoder(qc, Z, max_iter=mi, normalization=a.norm, early_stop=es)
+        if name == "qclms32":
+            return QCLayeredMSDecoder(qc, Z, max_iter=mi, normalization=a.norm, early_stop=es, dtype=np.float32)
         if name == "lms":
             return GenericOnQc(mi)
-        raise SystemExit("--qc takes --algo lms and qclms only, not %r" % spec)
-    if name == "qclms":
-        raise SystemExit("--algo qclms needs --qc mb,nb,Z,dv,seed")
+        raise SystemExit("--qc takes --algo lms, qclms and qclms32 only, not %r" % spec)
+    if name in ("qclms", "qclms32"):
+        raise SystemExit("--algo %s needs --qc mb,nb,Z,dv,seed" % name)
     if name == "bp":
         return BPDecoder(H, max_iter=mi, early_stop=es)
     if name == "ms":
@@ -102,13 +107,21 @@ if not a.n and qc is None and any(s.partition(":")[0] in ("ms", "lms") for s in 
                      "give --n N (a regular (3,6) code) with --algo ms / lms")
 decs = [make(s) for s in specs]
 llr = AWGNChannel(a.snr).llr_batch_device(cw, n, B, seed=4242)
+llr32 = llr.to(torch.float32) if any(s.partition(":")[0] == "qclms32" for s in specs) else None
+
+
+def frames_of(spec):
+    """The timed frames in the type the decoder reads: fp32 for qclms32 (cast above, once), else fp64."""
+    return llr32 if spec.partition(":")[0] == "qclms32" else llr
+
+
 out = torch.empty((B, n), dtype=torch.uint8, device="cuda")
 its = torch.empty((B,), dtype=torch.int32, device="cuda")
 stats = []
 results = {}
 for s, d in zip(specs, decs):  # warm-up: plan creation, workspace, first launch
     d._check_runnable()
-    d.plan.decode(llr, out, its)
+    d.plan.decode(frames_of(s), out, its)
     torch.cuda.synchronize()
     wrong = (out != 0).any(dim=1) if cw is None else None
     stats.append({"mean_iter": float(its.double().mean()),
@@ -120,13 +133,17 @@ if qc is not None:  # the two decoders are one definition: equal on the timed fr
     if "lms" in names and "qclms" in names:
         (b0, i0), (b1, i1) = results[names["lms"]], results[names["qclms"]]
         assert torch.equal(b0, b1) and torch.equal(i0, i1), "qclms and lms differ on the timed frames"
+    if "qclms" in names and "qclms32" in names:
+        (b0, _), (b1, _) = results[names["qclms"]], results[names["qclms32"]]
+        stats[specs.index(names["qclms32"])]["frames_differ_from_qclms"] = int((b0 != b1).any(dim=1).sum())
 times = [[] for _ in decs]
 for _ in range(a.rounds):
     for i, d in enumerate(decs):  # alternated, so drift hits every decoder alike
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         ev[0].record()
+        x = frames_of(specs[i])
         for _ in range(a.reps):
-            d.plan.decode(llr, out, its)
+            d.plan.decode(x, out, its)
         ev[1].record()
         torch.cuda.synchronize()
         times[i].append(ev[0].elapsed_time(ev[1]) / a.reps)
@@ -136,4 +153,6 @@ for s, d, t, st in zip(specs, decs, times, stats):
                       "kernel_ms_min": min(t), "kernel_ms_max": max(t), "info_mbps": B * k / ms / 1e3,
                       "mean_iter": st["mean_iter"], "frame_errors": st["frame_errors"],
                       "plan_kernel": int(d.plan.info.reserved), "lds_bytes": int(d.plan.info.lds_bytes),
+                      **({"frames_differ_from_qclms": st["frames_differ_from_qclms"]}
+                         if "frames_differ_from_qclms" in st else {}),
                       "kernel": os.environ.get("PL_LDPC_KERNEL", "default")}))
