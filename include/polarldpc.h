@@ -440,6 +440,79 @@ int pl_crc_append(uint8_t* msg_dev, int64_t ld, int64_t batch, int32_t k_data, i
 int pl_gf2_encode(const uint32_t* g_dev, int32_t k, int32_t n, const uint8_t* msg_dev, int64_t ld_msg,
                   int64_t batch, uint8_t* cw_dev, int64_t ld_cw, void* stream);
 
+/* ---- Quasi-cyclic LDPC encoder from the base matrix ------------------------------
+ * Valid codewords of the code pl_ldpc_qc_plan_create decodes, computed from the
+ * base matrix by cyclic shifts and XORs: no generator, H is never expanded.
+ *   shift[i * nb + j] as for pl_ldpc_qc_plan_create: H[i z + r, j z + (r + s) % z]
+ *   = 1, so check r of block row i reads sum_j c_j[(r + s_ij) % z] = 0, c_j the z
+ *   bits of block column j.  kb = nb - mb >= 1; k = kb z, n = nb z.  The message
+ *   occupies block columns 0 .. kb-1 and the code is systematic: cw[0:k] = msg.
+ * Supported structure of the parity part Hp = shift[:, kb:]: a core of g block rows
+ * followed by a lower-triangular extension, g == 0 or 3 <= g <= mb.
+ *   core rows (i < g):
+ *     - parity column kb has exactly three non-zero blocks, in rows 0, x and g-1
+ *       with 0 < x < g-1, of shifts (a, b, a): the first and the last are equal;
+ *     - parity column kb + t, t = 1 .. g-1, has exactly two non-zero blocks, in rows
+ *       t-1 and t, both of shift 0;
+ *     - core rows have no block in parity columns >= kb + g.
+ *   extension rows (g <= i < mb):
+ *     - shift[i][kb + i] >= 0 (any shift d_i), and no block to the right of it;
+ *     - any blocks in earlier columns, message or parity.
+ *   g == 0: a purely lower-triangular parity part; g == mb: the shape of IEEE
+ *   802.11n / 802.16e; g == 4 with degree-1 extension columns: the 5G NR shape.
+ *   g is unique: scanning the rows from the bottom while they satisfy the extension
+ *   condition, g = 0 if all do, else the last failing row is g - 2.  Hp is then
+ *   invertible: every message has exactly one codeword.
+ * Encoding (sums over GF(2); thread r handles check r of the current block row):
+ *   1. lambda_t[r] = sum_{j < kb} c_j[(r + s_tj) % z]        for each core row t
+ *   2. p_0[(r + b) % z] = sum_{t < g} lambda_t[r]
+ *   3. p_1[r] = lambda_0[r] + p_0[(r + a) % z]
+ *   4. p_{t+1}[r] = lambda_t[r] + p_t[r] + [t == x] p_0[(r + b) % z],  1 <= t <= g-2
+ *   5. p_i[(r + d_i) % z] = sum_{j < kb + i} c_j[(r + s_ij) % z]  for each extension
+ *      row i, in order (p_i: the bits of block column kb + i)
+ * PL_EINVAL for mb, nb or z < 1, kb < 1, nb z beyond int32, a shift outside
+ * -1 .. z-1; PL_EUNSUPPORTED for z > 1024, a parity part outside the structure (the
+ * message names the first rule violated) and a workgroup's LDS need above 160 KB.
+ * Every argument check runs before the first device call.  The encoder belongs
+ * to the device current at creation, as a plan does.
+ * One thread per check of the current block row; for z <= 64, 64 / z frames share
+ * a wavefront and up to four wavefronts a workgroup, else one workgroup of z
+ * threads (rounded up to 64) encodes a frame.  The codeword and the lambda_t live
+ * in LDS, one byte per bit, (nb + g) z bytes a frame (rounded up to 16). */
+typedef struct pl_qc_encoder pl_qc_encoder;
+int pl_ldpc_qc_encoder_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift /* [mb*nb] row-major */,
+                              pl_qc_encoder** out);
+/* msg_dev uint8 [batch][ld_msg] device, ld_msg >= k, bit 0 of each byte is the
+ * message bit; cw_dev uint8 [batch][ld_cw] device, ld_cw >= n: the n codeword
+ * bytes (0 / 1) of each row are written, bytes beyond n are left alone.
+ * Asynchronous on `stream`; batch == 0 launches nothing.  PL_EINVAL for a NULL
+ * pointer, ld_msg < k, ld_cw < n, batch < 0, or a current device other than the
+ * encoder's. */
+int pl_ldpc_qc_encode(const pl_qc_encoder* enc, const uint8_t* msg_dev, int64_t ld_msg, int64_t batch,
+                      uint8_t* cw_dev, int64_t ld_cw, void* stream);
+int pl_ldpc_qc_encoder_destroy(pl_qc_encoder* enc);
+/* What the planner decides for an encoder, with no device call (pl_ldpc_qc_encoder_create's checks,
+ * codes and messages).  The stream the kernel walks, int32 words:
+ *   g, x, a, b                       (x, a, b are 0 when g == 0)
+ *   per core row t = 0 .. g-1:       d, then d (block column, shift) pairs: its message blocks, ascending
+ *   per extension row i = g .. mb-1: d_i, the sync flag, d, then d (block column, shift) pairs: its blocks
+ *                                    left of the diagonal, ascending block column
+ * sync flag: 1 iff the row reads a parity block column written since the last synchronisation point.
+ * n_sync: the synchronisation points the stream asks for, the one behind p_0 (g > 0) plus the flagged
+ * extension rows (those around loading the message and storing the codeword are not counted). */
+typedef struct {
+    int32_t g, x, a, b;
+    int32_t subwave;     /* 1: z <= 64, frames share wavefronts                         */
+    int32_t fpw, fpb;    /* frames per wavefront, wavefronts per workgroup              */
+    int32_t threads, lds_bytes, n_sync;
+    int64_t table_len;   /* int32 words of the stream                                   */
+    uint64_t digest;     /* 64-bit FNV-1a over the stream's bytes                       */
+} pl_qc_encoder_probe;
+int pl_debug_ldpc_qc_encoder_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift, pl_qc_encoder_probe* out);
+/* Test hook, diagnostic build only (the product library returns PL_EUNSUPPORTED):
+ * pl_debug_set_plan_device for an encoder. */
+int pl_debug_set_qc_encoder_device(pl_qc_encoder* enc, int32_t device);
+
 /* Error counting (benchmarks/ber_simulation.py:180-189):
  * counts_dev[0] += bit errors, [1] += frame errors, [2] += frames, over the
  * first `width` entries of each row.  counts_dev int64[3], device. */

@@ -29,6 +29,8 @@ EXPORTS = (
     "pl_debug_polar_flagged", "pl_polar_plan_small_batch", "pl_ldpc_layered_plan_create", "pl_ldpc_decode_soft",
     "pl_debug_ldpc_plan_probe", "pl_debug_ldpc_layered_plan_probe", "pl_ldpc_qc_plan_create",
     "pl_debug_ldpc_qc_plan_probe", "pl_ldpc_decode_f32", "pl_debug_ldpc_qc_plan_probe_flags",
+    "pl_ldpc_qc_encoder_create", "pl_ldpc_qc_encode", "pl_ldpc_qc_encoder_destroy", "pl_debug_ldpc_qc_encoder_probe",
+    "pl_debug_set_qc_encoder_device",
 )
 
 
@@ -62,6 +64,13 @@ class LdpcQcPlanProbe(ctypes.Structure):
                [("digest", ctypes.c_uint64)]
 
 
+class QcEncoderProbe(ctypes.Structure):
+    """pl_qc_encoder_probe: the quasi-cyclic encoder's structure, geometry and stream."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("g", "x", "a", "b", "subwave", "fpw", "fpb", "threads", "lds_bytes",
+                                              "n_sync")] + \
+               [("table_len", ctypes.c_int64), ("digest", ctypes.c_uint64)]
+
+
 def _load(path=LIB_PATH):
     if not os.path.exists(path):
         raise ImportError(
@@ -81,6 +90,11 @@ def _load(path=LIB_PATH):
     L.pl_debug_ldpc_qc_plan_probe.argtypes = [I32, I32, I32, P, P, I32, I32, D, I32, ctypes.POINTER(LdpcQcPlanProbe)]
     L.pl_debug_ldpc_qc_plan_probe_flags.argtypes = [I32, I32, I32, P, P, I32, I32, D, I32, I32,
                                                     ctypes.POINTER(LdpcQcPlanProbe)]
+    L.pl_ldpc_qc_encoder_create.argtypes = [I32, I32, I32, P, PP]
+    L.pl_ldpc_qc_encode.argtypes = [P, P, I64, I64, P, I64, P]
+    L.pl_ldpc_qc_encoder_destroy.argtypes = [P]
+    L.pl_debug_ldpc_qc_encoder_probe.argtypes = [I32, I32, I32, P, ctypes.POINTER(QcEncoderProbe)]
+    L.pl_debug_set_qc_encoder_device.argtypes = [P, I32]
     L.pl_ldpc_decode_soft.argtypes = [P, P, I64, I64, P, P, P, I64, P]
     L.pl_ldpc_decode_f32.argtypes = [P, P, I64, I64, P, P, P, I64, P, I64, P]
     L.pl_decode.argtypes = [P, P, I64, I64, P, P, P]
@@ -363,6 +377,49 @@ def qc_ldpc_plan(base: np.ndarray, Z: int, layer_order, max_iter: int, early_sto
                                      int(bool(early_stop)), float(normalization), int(flags), ctypes.byref(h)),
           "pl_ldpc_qc_plan_create")
     return Plan(h)
+
+
+class QcEncoder:
+    """Owner of a pl_qc_encoder* (pl_ldpc_qc_encoder_create): the device stream of a
+    base matrix of the encodable structure, bound to the device current at creation."""
+
+    def __init__(self, handle: ctypes.c_void_p, k: int, n: int):
+        self._h, self.k, self.n = handle, k, n
+
+    @property
+    def handle(self):
+        return self._h
+
+    def encode(self, msg: "torch.Tensor", cw: "torch.Tensor", stream=None):
+        """msg uint8 [B, k], cw uint8 [B, n]: device tensors with unit inner stride, any row pitch."""
+        assert msg.dtype == torch.uint8 and cw.dtype == torch.uint8 and msg.dim() == 2 and cw.dim() == 2
+        assert msg.shape == (cw.shape[0], self.k) and cw.shape[1] == self.n
+        if msg.shape[0] == 0:
+            return
+        check(lib.pl_ldpc_qc_encode(self._h, _dptr(msg), _ld(msg), msg.shape[0], _dptr(cw), _ld(cw),
+                                    ctypes.c_void_p(_stream(stream))), "pl_ldpc_qc_encode")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.pl_ldpc_qc_encoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def qc_encoder(base: np.ndarray, Z: int) -> QcEncoder:
+    """pl_ldpc_qc_encoder_create; base: int [mb, nb] shifts (-1: zero block) of the encodable structure."""
+    sh = np.ascontiguousarray(base, dtype=np.int32)
+    assert sh.ndim == 2, "base must be [mb, nb]"
+    require_gpu()
+    h = ctypes.c_void_p()
+    check(lib.pl_ldpc_qc_encoder_create(sh.shape[0], sh.shape[1], int(Z), sh.ctypes.data_as(ctypes.c_void_p),
+                                        ctypes.byref(h)), "pl_ldpc_qc_encoder_create")
+    return QcEncoder(h, (sh.shape[1] - sh.shape[0]) * int(Z), sh.shape[1] * int(Z))
 
 
 def random_bits(seed: int, frame_offset: int, bits: "torch.Tensor", stream=None):

@@ -6,6 +6,6 @@ _ROOT = str(_Path(__file__).resolve().parents[4])
 if _ROOT not in _sys.path:
     _sys.path.insert(0, _ROOT)
 
-from polarcode_and_ldpc_amd.ldpc.encoder import LDPCEncoder  # noqa: F401
+from polarcode_and_ldpc_amd.ldpc.encoder import LDPCEncoder, QCLDPCEncoder  # noqa: F401
 
-__all__ = ['LDPCEncoder']
+__all__ = ['LDPCEncoder', 'QCLDPCEncoder']

@@ -1076,6 +1076,92 @@ extern "C" int pl_gf2_encode(const uint32_t* g_dev, int32_t k, int32_t n, const 
     return PL_OK;
 }
 
+// ---- quasi-cyclic encoder from the base matrix (ldpc_qc_encode.hip) ----
+struct pl_qc_encoder {
+    int device = 0;
+    pl::QcEncGeom g{};
+    int32_t* d_tab = nullptr;  // the planner's stream
+};
+
+extern "C" int pl_ldpc_qc_encoder_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                         pl_qc_encoder** out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    *out = nullptr;
+    // every argument check (ldpc_plan.cpp) comes before the first device call
+    pl::QcEncHostPlan hp;
+    const pl::PlanStatus st = pl::qc_encoder_plan_build(mb, nb, z, shift, &hp);
+    if (st.code) return fail(st.code, st.msg);
+    int dev = -1;
+    const hipError_t ge = hipGetDevice(&dev);
+    if (ge != hipSuccess) return hipfail(ge, "hipGetDevice");
+    pl_qc_encoder* e = new pl_qc_encoder();
+    e->g = hp.geom;
+    e->device = dev;
+    hipError_t err = upload(&e->d_tab, hp.tables);
+    if (err == hipSuccess) err = pl::qc_encode_prepare(e->g);
+    if (err != hipSuccess) {
+        pl_ldpc_qc_encoder_destroy(e);
+        return hipfail(err, "encoder upload");
+    }
+    *out = e;
+    return PL_OK;
+}
+
+extern "C" int pl_ldpc_qc_encode(const pl_qc_encoder* enc, const uint8_t* msg, int64_t ld_msg, int64_t batch,
+                                 uint8_t* cw, int64_t ld_cw, void* stream) {
+    if (!enc) return fail(PL_EINVAL, "encoder is NULL");
+    if (!msg || !cw) return fail(PL_EINVAL, "msg_dev and cw_dev must not be NULL");
+    if (batch < 0) return fail(PL_EINVAL, "batch must be >= 0");
+    if (ld_msg < enc->g.k) return fail(PL_EINVAL, "ld_msg < k = " + std::to_string(enc->g.k));
+    if (ld_cw < enc->g.n) return fail(PL_EINVAL, "ld_cw < n = " + std::to_string(enc->g.n));
+    int cur = -1;
+    const hipError_t ge = hipGetDevice(&cur);
+    if (ge != hipSuccess) return hipfail(ge, "hipGetDevice");
+    if (cur != enc->device)
+        return fail(PL_EINVAL, "current device " + std::to_string(cur) + " is not the encoder's device " +
+                                   std::to_string(enc->device) + " (hipSetDevice first)");
+    // whole workgroups per launch, below kMaxLaunchItems work-items
+    const int64_t step = kMaxLaunchItems / enc->g.threads * ((int64_t)enc->g.fpw * enc->g.fpb);
+    for (int64_t b0 = 0; b0 < batch; b0 += step) {
+        const int64_t nb = std::min<int64_t>(step, batch - b0);
+        const hipError_t e = pl::qc_encode_launch(enc->g, enc->d_tab, msg + b0 * ld_msg, ld_msg, nb, cw + b0 * ld_cw,
+                                                  ld_cw, (hipStream_t)stream);
+        if (e != hipSuccess) return hipfail(e, "qc encode launch");
+    }
+    return PL_OK;
+}
+
+extern "C" int pl_ldpc_qc_encoder_destroy(pl_qc_encoder* enc) {
+    if (!enc) return PL_OK;
+    if (enc->d_tab) hipFree(enc->d_tab);
+    delete enc;
+    return PL_OK;
+}
+
+// The planner's decisions for an encoder, with no device call.
+extern "C" int pl_debug_ldpc_qc_encoder_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                              pl_qc_encoder_probe* out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    pl::QcEncHostPlan hp;
+    const pl::PlanStatus st = pl::qc_encoder_plan_build(mb, nb, z, shift, &hp);
+    if (st.code) return fail(st.code, st.msg);
+    const pl::QcEncGeom& g = hp.geom;
+    *out = pl_qc_encoder_probe{g.g, hp.x, hp.a, hp.b, g.subwave, g.fpw, g.fpb, g.threads, g.lds_bytes, hp.n_sync,
+                               (int64_t)hp.tables.size(), pl::plan_tables_digest(hp.tables)};
+    return PL_OK;
+}
+
+extern "C" int pl_debug_set_qc_encoder_device(pl_qc_encoder* enc, int32_t device) {
+    if (!enc) return fail(PL_EINVAL, "encoder is NULL");
+#if !PL_DIAG
+    (void)device;
+    return fail(PL_EUNSUPPORTED, "test hook: diagnostic build only (make DIAG=1)");
+#else
+    enc->device = device;
+    return PL_OK;
+#endif
+}
+
 extern "C" int pl_count_errors(const uint8_t* ref, int64_t ldr, const uint8_t* dec, int64_t ldd, int32_t width,
                                int64_t batch, int64_t* counts, void* stream) {
     if (batch < 0 || width < 0 || !counts || (batch > 0 && (!ref || !dec))) return fail(PL_EINVAL, "bad argument");

@@ -144,4 +144,10 @@ hipError_t qc_launch(const QcGeom& g, bool f32, const int32_t* tab, const double
 hipError_t qc_launch(const QcGeom& g, const int32_t* tab, const float* llr, int64_t ld, uint8_t* bits, int32_t* iters,
                      float* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
 
+// ---- quasi-cyclic encoder from the base matrix (ldpc_qc_encode.hip); QcEncGeom: ldpc_plan.hpp ----
+hipError_t qc_encode_prepare(const QcEncGeom& g);
+// tab: the plan's stream (device); msg uint8 [batch][ldm] (bit 0 of each byte), cw uint8 [batch][ldc]
+hipError_t qc_encode_launch(const QcEncGeom& g, const int32_t* tab, const uint8_t* msg, int64_t ldm, int64_t batch,
+                            uint8_t* cw, int64_t ldc, hipStream_t s);
+
 }  // namespace pl

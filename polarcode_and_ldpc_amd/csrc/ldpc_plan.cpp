@@ -3,7 +3,8 @@
 // tables, kernel selection, the degree-grouped BP tables, the (3,6) min-sum
 // address words, all packed into one vector.  Layered plans: layer checks and
 // the kernel geometry.  Quasi-cyclic layered plans: base-matrix checks, the
-// geometry and the per-layer (block column, shift) stream.
+// geometry and the per-layer (block column, shift) stream.  Quasi-cyclic encoder
+// plans: the core-plus-extension structure of the parity part and the encoder's stream.
 #include "ldpc_plan.hpp"
 
 #include <algorithm>
@@ -514,6 +515,127 @@ PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int3
             if (s >= 0) { t.push_back(j); t.push_back(s); }
         }
         t[at + 1] = (int32_t)((t.size() - at - 2) / 2);
+    }
+    return {};
+}
+
+// ---- quasi-cyclic encoder plans ----
+
+PlanStatus qc_encoder_plan_build(int mb, int nb, int z, const int32_t* shift, QcEncHostPlan* out) {
+    if (mb < 1 || nb < 1 || z < 1 || !shift) return refuse(PL_EINVAL, "mb, nb and Z must be >= 1");
+    const int kb = nb - mb;
+    if (kb < 1) return refuse(PL_EINVAL, "kb = nb - mb must be >= 1 (no message block column)");
+    if ((int64_t)nb * z > INT32_MAX) return refuse(PL_EINVAL, "nb Z must fit 32 bits");
+    size_t blocks = 0;
+    for (int i = 0; i < mb; ++i)
+        for (int j = 0; j < nb; ++j) {
+            const int s = shift[(size_t)i * nb + j];
+            if (s < -1 || s >= z)
+                return refuse(PL_EINVAL, "shift of block (" + std::to_string(i) + ", " + std::to_string(j) +
+                                             ") outside -1 .. Z-1");
+            blocks += s >= 0;
+        }
+    if (z > kQcMaxZ) return refuse(PL_EUNSUPPORTED, "Z > 1024");
+
+    // the structure: P(i, t) is the block of row i in parity column kb + t
+    auto P = [&](int i, int t) { return shift[(size_t)i * nb + kb + t]; };
+    auto row = [](int i) { return "block row " + std::to_string(i); };
+    auto pcol = [](int t) { return "parity column kb+" + std::to_string(t); };
+    auto ext_ok = [&](int i) {
+        if (P(i, i) < 0) return false;
+        for (int t = i + 1; t < mb; ++t)
+            if (P(i, t) >= 0) return false;
+        return true;
+    };
+    int f = mb - 1;
+    while (f >= 0 && ext_ok(f)) --f;
+    const int g = f < 0 ? 0 : f + 2;  // the last row that is no extension row is core row g - 2
+    int x = 0, a = 0, b = 0;
+    if (g > mb)
+        return refuse(PL_EUNSUPPORTED, row(f) + " is no extension row (a diagonal block and none to its right) and "
+                                           "cannot be the last but one row of a core");
+    if (g == 2) return refuse(PL_EUNSUPPORTED, "a core of g = 2 block rows: g must be 0 or >= 3");
+    if (g > 0) {
+        for (int i = 0; i < g; ++i)
+            for (int t = g; t < mb; ++t)
+                if (P(i, t) >= 0) return refuse(PL_EUNSUPPORTED, "core " + row(i) + " has a block in " + pcol(t));
+        int cnt = 0;
+        for (int i = 0; i < g; ++i) cnt += P(i, 0) >= 0;
+        if (P(0, 0) < 0 || P(g - 1, 0) < 0 || cnt != 3)
+            return refuse(PL_EUNSUPPORTED, pcol(0) + " must have exactly three blocks in the core, in rows 0, x and g-1 = " +
+                                               std::to_string(g - 1) + " (it has " + std::to_string(cnt) + ")");
+        for (int i = 1; i < g - 1; ++i)
+            if (P(i, 0) >= 0) x = i;
+        a = P(0, 0);
+        b = P(x, 0);
+        if (P(g - 1, 0) != a)
+            return refuse(PL_EUNSUPPORTED, "the first and the last block of " + pcol(0) + " must have equal shifts (" +
+                                               std::to_string(a) + ", " + std::to_string(P(g - 1, 0)) + ")");
+        for (int t = 1; t < g; ++t)
+            for (int i = 0; i < g; ++i) {
+                const bool want = i == t - 1 || i == t;
+                if ((P(i, t) >= 0) != want)
+                    return refuse(PL_EUNSUPPORTED, pcol(t) + " must have exactly two blocks in the core, in rows " +
+                                                       std::to_string(t - 1) + " and " + std::to_string(t));
+                if (want && P(i, t) != 0)
+                    return refuse(PL_EUNSUPPORTED, "the dual-diagonal block (" + std::to_string(i) + ", kb+" +
+                                                       std::to_string(t) + ") must have shift 0");
+            }
+    }
+
+    QcEncGeom& q = out->geom;
+    q = QcEncGeom{};
+    q.mb = mb; q.nb = nb; q.kb = kb; q.z = z; q.k = kb * z; q.n = nb * z; q.g = g;
+    const int64_t frame = (int64_t)ldpc_align16((size_t)(nb + g) * (size_t)z);
+    q.subwave = z <= 64 ? 1 : 0;
+    q.fpw = q.subwave ? 64 / z : 1;
+    const int64_t wave = frame * q.fpw;
+    if (wave > kQcEncLdsMax)
+        return refuse(PL_EUNSUPPORTED, "the codeword and the core sums of a workgroup, " + std::to_string(wave) +
+                                           " bytes, exceed 160 KB of LDS");
+    q.fpb = q.subwave ? (int)std::max<int64_t>(1, std::min<int64_t>(4, 65536 / wave)) : 1;
+    q.threads = q.subwave ? 64 * q.fpb : (z + 63) / 64 * 64;
+    q.frame_bytes = (int)frame;
+    q.lds_bytes = (int)(wave * q.fpb);
+    out->x = x; out->a = a; out->b = b;
+
+    std::vector<int32_t>& t = out->tables;
+    t.clear();
+    t.reserve(4 + 3 * (size_t)mb + 2 * blocks);
+    t.insert(t.end(), {g, x, a, b});
+    for (int i = 0; i < g; ++i) {
+        const size_t at = t.size();
+        t.push_back(0);
+        for (int j = 0; j < kb; ++j) {
+            const int s = shift[(size_t)i * nb + j];
+            if (s >= 0) { t.push_back(j); t.push_back(s); }
+        }
+        t[at] = (int32_t)((t.size() - at - 1) / 2);
+    }
+    // parity block columns written since the last synchronisation point: behind p_0's the chain p_1 .. p_{g-1}
+    std::vector<uint8_t> dirty((size_t)mb, 0);
+    for (int i = 1; i < g; ++i) dirty[i] = 1;
+    out->n_sync = g > 0 ? 1 : 0;
+    for (int i = g; i < mb; ++i) {
+        const size_t at = t.size();
+        t.push_back(P(i, i));
+        t.push_back(0);
+        t.push_back(0);
+        bool sync = false;
+        for (int j = 0; j < kb + i; ++j) {
+            const int s = shift[(size_t)i * nb + j];
+            if (s < 0) continue;
+            t.push_back(j);
+            t.push_back(s);
+            sync |= j >= kb && dirty[j - kb];
+        }
+        t[at + 1] = sync ? 1 : 0;
+        t[at + 2] = (int32_t)((t.size() - at - 3) / 2);
+        if (sync) {
+            std::fill(dirty.begin(), dirty.end(), 0);
+            ++out->n_sync;
+        }
+        dirty[i] = 1;
     }
     return {};
 }

@@ -223,6 +223,46 @@ struct QcHostPlan {
 PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order, int max_iter,
                          int early_stop, double norm, const LdpcPlanOptions& opt, QcHostPlan* out);
 
+// ---- quasi-cyclic encoder from the base matrix (ldpc_qc_encode.hip) ----
+// The supported structure and the encoding steps: include/polarldpc.h,
+// pl_ldpc_qc_encoder_create.  kb = nb - mb message block columns, then mb parity
+// block columns: a core of g block rows (g == 0 or g >= 3) and a lower-triangular
+// extension.  Per frame the LDS holds the codeword, one byte per bit, and behind it
+// the g vectors lambda_t: (nb + g) z bytes, rounded up to 16.
+struct QcEncGeom {
+    int mb, nb, kb, z, k, n;
+    int g;            // core block rows
+    int subwave;      // 1 (z <= 64): fpw frames share a wavefront; 0: one workgroup per frame
+    int fpw;          // frames per wavefront (64 / z; 1 when !subwave)
+    int fpb;          // wavefronts per workgroup when subwave, else 1: a workgroup encodes fpw fpb frames
+    int threads;
+    int frame_bytes;  // LDS bytes of a frame: align16((nb + g) z)
+    int lds_bytes;    // fpw fpb frame_bytes
+};
+constexpr int kQcEncLdsMax = 160 * 1024;
+struct QcEncHostPlan {
+    QcEncGeom geom{};
+    int x = 0, a = 0, b = 0;  // the core's middle row of parity column kb and its shifts (0 when g == 0)
+    int n_sync = 0;           // synchronisation points the stream asks for: the one behind p_0 (g > 0)
+                              // and one per extension row whose sync flag is set
+    // One stream, walked front to back at wave-uniform addresses:
+    //   g, x, a, b
+    //   per core row t = 0 .. g-1:     d, then d (block column, shift) pairs -- its message blocks
+    //                                  (block column < kb), ascending block column
+    //   per extension row i = g .. mb-1: the diagonal shift d_i, the sync flag, d, then d (block column,
+    //                                  shift) pairs -- its blocks left of the diagonal (block column <
+    //                                  kb + i, message or parity), ascending block column
+    // The sync flag is 1 iff the row reads a parity block column written since the last
+    // synchronisation point; the kernel synchronises before such a row and nowhere else in the
+    // extension.  4 + g + 3 (mb - g) + 2 (blocks in the stream) words.
+    std::vector<int32_t> tables;
+};
+// Encoder plan for the base matrix shift [mb][nb] (row-major, -1 a zero block): pl_ldpc_qc_encoder_create's
+// checks.  PL_EINVAL: mb, nb or z < 1, kb = nb - mb < 1, nb z beyond int32, a shift outside -1 .. z-1;
+// PL_EUNSUPPORTED: z > kQcMaxZ, a parity part outside the structure (the message names the first rule
+// violated), a workgroup's LDS above kQcEncLdsMax.
+PlanStatus qc_encoder_plan_build(int mb, int nb, int z, const int32_t* shift, QcEncHostPlan* out);
+
 // 64-bit FNV-1a over a table vector's bytes (the pl_debug_*_plan_probe digests)
 uint64_t plan_tables_digest(const std::vector<int32_t>& tables);
 

@@ -12,8 +12,10 @@ Code choices follow the reference's simulate_* (:132-293): polar frozen set from
 PolarLibWrapper(N, K, 2.0) (offline substitute: bit-reversed Bhattacharyya),
 LDPC H from LDPCLibWrapper(n, k, dv, dc, seed=42) (offline substitute), BP with
 max_iterations, errors over the k message positions.  LDPC frames use the
-all-zero codeword (BP is codeword-symmetric); polar frames use random messages
-through the device encoder.
+all-zero codeword (BP is codeword-symmetric) or, on request, random messages
+through a device encoder; polar frames use random messages through the device
+encoder.  simulate_qc_ldpc is the same for a quasi-cyclic code given by its base
+matrix (layered min-sum, fp64 or fp32; codewords from QCLDPCEncoder).
 """
 from __future__ import annotations
 
@@ -95,6 +97,31 @@ def simulate_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: in
     return np.array([p.ber for p in pts]), np.array([p.fer for p in pts]), pts
 
 
+def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: int, base, Z: int,
+                     max_iter: int = 20, normalization: float = 0.75, dtype=np.float64, batch: int = 65536,
+                     seed: int = 0, group=None, random_codewords: bool = False, log_path=None):
+    """simulate_ldpc for the quasi-cyclic code (base, Z): QCLayeredMSDecoder (layered
+    normalised min-sum, early stop, state in `dtype`) on frames of the all-zero
+    codeword or, random_codewords, of random messages encoded on the device from
+    the base matrix (QCLDPCEncoder: base must have its structure, e.g. from
+    qc_encodable_base).  H is never expanded.  -> (ber, fer, points), errors over
+    the k = (nb - mb) Z message positions."""
+    import torch
+    from ..ldpc.decoder import QCLayeredMSDecoder
+    from ..ldpc.encoder import QCLDPCEncoder
+    base = np.asarray(base, dtype=np.int64)
+    dec = QCLayeredMSDecoder(base, Z, max_iter=max_iter, normalization=normalization, early_stop=True, dtype=dtype)
+    k = dec.n - dec.m
+    enc = QCLDPCEncoder(base, Z) if random_codewords else None
+    mc = MonteCarlo(ldpc_round_fn(dec, seed=seed, info_bits=k, encoder=enc), info_bits=k, batch=batch, group=group,
+                    device=torch.device("cuda", torch.cuda.current_device()))
+    log = _log(log_path, mc, code="qcldpc", n=dec.n, k=k, Z=int(Z), max_iter=max_iter, norm=float(normalization),
+               dtype=np.dtype(dec.dtype).name, random=random_codewords, frames=num_frames, max_errors=max_errors,
+               seed=seed, base=_digest(base + 1))
+    pts = mc.run(snr_db_range, num_frames, max_errors, log=log)
+    return np.array([p.ber for p in pts]), np.array([p.fer for p in pts]), pts
+
+
 def run_ber_simulation(snr_db_range: np.ndarray, num_frames: int, max_errors: int, polar_config: Dict,
                        ldpc_config: Dict, output_dir: Path, use_third_party: bool = False, batch: int = 65536,
                        list_size: int = 0, crc_polynomial: Optional[str] = None, resume: bool = False) -> Dict:
@@ -123,14 +150,16 @@ def _parse_range(s: str):
 def main(argv=None):
     """CLI (one process per GPU under torchrun; RCCL all-reduce of the counters):
     python -m polarcode_and_ldpc_amd.harness.ber --code polar --N 1024 --K 512 \\
-        --list-size 32 --crc CRC-8 --snr=-2:5:1 --frames 1000000 --max-errors 100"""
+        --list-size 32 --crc CRC-8 --snr=-2:5:1 --frames 1000000 --max-errors 100
+    python -m polarcode_and_ldpc_amd.harness.ber --code qcldpc --qc 12,24,81,3,1 --ldpc-codewords random \\
+        --dtype float32 --norm 0.75 --snr=-1.25:-0.75:0.25 --frames 524288 --max-errors 1000000"""
     import argparse
     import json
     import os
     import torch
     import torch.distributed as dist
     ap = argparse.ArgumentParser()
-    ap.add_argument("--code", choices=["polar", "ldpc"], default="polar")
+    ap.add_argument("--code", choices=["polar", "ldpc", "qcldpc"], default="polar")
     ap.add_argument("--N", type=int, default=1024)
     ap.add_argument("--K", type=int, default=512)
     ap.add_argument("--list-size", type=int, default=0)
@@ -148,6 +177,12 @@ def main(argv=None):
                          "--resume-log: torchrun's own parser takes --log for an abbreviation of --log-dir)")
     ap.add_argument("--ldpc-codewords", choices=["zero", "random"], default="zero",
                     help="LDPC frames: all-zero codeword, or random messages encoded on the device")
+    ap.add_argument("--qc", default="12,24,81,3,1",
+                    help="--code qcldpc: mb,nb,Z,dv,seed[,core], the code qc_encodable_base(mb, nb, Z, dv, seed, core)")
+    ap.add_argument("--dtype", choices=["float64", "float32"], default="float64",
+                    help="--code qcldpc: the decoder's state and arithmetic")
+    ap.add_argument("--norm", type=float, default=0.75, help="--code qcldpc: min-sum normalisation")
+    ap.add_argument("--seed", type=int, default=0, help="--code qcldpc: seed of the frame source")
     ap.add_argument("--cpu-stub", action="store_true",
                     help="plumbing check on CPU: gloo ranks and a deterministic stub round function "
                          "(montecarlo.stub_round_fn) instead of the device decoders; not a simulation")
@@ -171,6 +206,15 @@ def main(argv=None):
     elif a.code == "polar":
         ber, fer, pts = simulate_polar(snr, a.frames, a.max_errors, {"encoding": {"N": a.N, "K": a.K}},
                                        a.list_size, a.crc, a.batch, log_path=a.log)
+    elif a.code == "qcldpc":
+        from ..ldpc.matrix import qc_encodable_base
+        q = [int(x) for x in a.qc.split(",")]
+        if len(q) not in (5, 6):
+            ap.error("--qc takes mb,nb,Z,dv,seed[,core]")
+        base = qc_encodable_base(*q[:5], core=q[5] if len(q) == 6 else None)
+        ber, fer, pts = simulate_qc_ldpc(snr, a.frames, a.max_errors, base, q[2], max_iter=a.max_iter,
+                                         normalization=a.norm, dtype=np.dtype(a.dtype).type, batch=a.batch,
+                                         seed=a.seed, random_codewords=a.ldpc_codewords == "random", log_path=a.log)
     else:
         ber, fer, pts = simulate_ldpc(snr, a.frames, a.max_errors,
                                       {"encoding": {"n": a.n, "k": a.k}, "decoding": {"max_iterations": a.max_iter}},

@@ -1,13 +1,15 @@
 """LDPC codes: drop-in BP / Min-Sum decoders (HIP) + parity-check matrices."""
 from .decoder import BPDecoder, LayeredMSDecoder, MSDecoder, QCLayeredMSDecoder
-from .encoder import LDPCEncoder, valid_generator
+from .encoder import LDPCEncoder, QCLDPCEncoder, valid_generator
 from .matrix import (calculate_girth, check_matrix_rank, create_systematic_generator, csr_to_dense, dense_to_csr,
                      generate_ldpc_matrix, gf2_systematic_pair, layer_schedule, mackay_construction, peg_construction,
-                     qc_block_layers, qc_expand, qc_random_base, qc_to_csr, regular_construction)
+                     qc_block_layers, qc_encodable_base, qc_encoding_structure, qc_expand, qc_random_base, qc_to_csr,
+                     regular_construction)
 from .utils import calculate_syndrome, check_syndrome, count_errors, create_tanner_graph, hamming_distance
 
-__all__ = ["BPDecoder", "MSDecoder", "LayeredMSDecoder", "QCLayeredMSDecoder", "LDPCEncoder", "dense_to_csr", "csr_to_dense",
+__all__ = ["BPDecoder", "MSDecoder", "LayeredMSDecoder", "QCLayeredMSDecoder", "LDPCEncoder", "QCLDPCEncoder", "dense_to_csr", "csr_to_dense",
            "generate_ldpc_matrix", "mackay_construction", "regular_construction", "peg_construction",
            "layer_schedule", "create_systematic_generator", "check_matrix_rank", "calculate_girth",
            "gf2_systematic_pair", "create_tanner_graph", "check_syndrome", "calculate_syndrome", "count_errors",
-           "hamming_distance", "qc_expand", "qc_to_csr", "qc_block_layers", "qc_random_base"]
+           "hamming_distance", "qc_expand", "qc_to_csr", "qc_block_layers", "qc_random_base",
+           "qc_encodable_base", "qc_encoding_structure"]

@@ -9,7 +9,9 @@ vectorised back-substitution) -- giving exactly the reference's
 codewords, including the *invalid* ones it emits for the seed-42 (504, 252) H
 (SURVEY.md §0 quirk 2), which is what benchmarks/throughput_test.py decodes.
 `valid_generator` / `LDPCEncoder.encode_batch_device` add encoding into valid
-codewords on the device (pl_gf2_encode).
+codewords on the device (pl_gf2_encode).  QCLDPCEncoder encodes a quasi-cyclic
+code from its base matrix, on the host and on the device (pl_ldpc_qc_encode),
+without a generator.
 """
 from __future__ import annotations
 
@@ -17,7 +19,7 @@ from typing import Optional
 
 import numpy as np
 
-from .matrix import generate_ldpc_matrix
+from .matrix import generate_ldpc_matrix, qc_encoding_structure, qc_expand
 
 
 def _systematic_generator(H: np.ndarray):
@@ -214,3 +216,108 @@ class LDPCEncoder:
 
     def __repr__(self) -> str:
         return f"LDPCEncoder(n={self.n}, k={self.k}, rate={self.get_code_rate():.3f})"
+
+
+class QCLDPCEncoder:
+    """Encoder of the quasi-cyclic code (base, Z) from its base matrix: the parity
+    blocks follow from the message blocks by cyclic shifts and XORs in block-row
+    order (include/polarldpc.h, pl_ldpc_qc_encoder_create: the supported
+    structure -- a core of g block rows and a lower-triangular extension, see
+    qc_encoding_structure -- and the steps).  No generator; H is never expanded
+    unless `.H` is read.  Systematic: codeword[:k] = message, k = (nb - mb) Z.
+    ValueError for a base outside the structure.
+
+    encode / encode_batch run on the host (NumPy, block-wise index arithmetic),
+    encode_batch_device on the device (pl_ldpc_qc_encode) with
+    LDPCEncoder.encode_batch_device's contract, so harness.ldpc_round_fn(decoder,
+    encoder=QCLDPCEncoder(base, Z)) draws random codewords of the decoder's code."""
+
+    def __init__(self, base: np.ndarray, Z: int):
+        self.base = np.array(base, dtype=np.int64)
+        if self.base.ndim != 2 or self.base.size == 0:
+            raise ValueError("base must be [mb, nb]")
+        self.Z = int(Z)
+        if not 1 <= self.Z <= 1024:
+            raise ValueError("Z must lie in 1 .. 1024")
+        if np.any((self.base < -1) | (self.base >= self.Z)):
+            raise ValueError("base entries must lie in -1 .. Z-1")
+        self.g, self.x = qc_encoding_structure(self.base)
+        self.mb, self.nb = self.base.shape
+        self.kb = self.nb - self.mb
+        self.m, self.n, self.k = self.mb * self.Z, self.nb * self.Z, self.kb * self.Z
+        frame = ((self.nb + self.g) * self.Z + 15) // 16 * 16  # the planner's rule (csrc/ldpc_plan.cpp)
+        if frame * (64 // self.Z if self.Z <= 64 else 1) > 160 * 1024:
+            raise ValueError("the codeword and the core sums, (nb + g) Z bytes a frame, exceed 160 KB of LDS")
+        self.info_positions = np.arange(self.k)
+        self._H = None
+        self._enc = {}  # device index -> _native.QcEncoder
+
+    @property
+    def H(self) -> np.ndarray:
+        if self._H is None:
+            self._H = qc_expand(self.base, self.Z)
+        return self._H
+
+    def _row(self, c: np.ndarray, i: int, ncols: int) -> np.ndarray:
+        """[B, Z]: sum over the blocks of row i in block columns < ncols of c_j[(r + s_ij) % Z]."""
+        acc = np.zeros((c.shape[0], self.Z), dtype=np.uint8)
+        for j in np.nonzero(self.base[i, :ncols] >= 0)[0]:
+            acc ^= np.roll(c[:, j], -int(self.base[i, j]), axis=1)
+        return acc
+
+    def encode_batch(self, messages: np.ndarray) -> np.ndarray:
+        msg = (np.asarray(messages, dtype=np.int64) & 1).astype(np.uint8)
+        assert msg.ndim == 2 and msg.shape[1] == self.k, f"messages must be [B, {self.k}]"
+        kb, g, Z = self.kb, self.g, self.Z
+        c = np.zeros((msg.shape[0], self.nb, Z), dtype=np.uint8)
+        c[:, :kb] = msg.reshape(-1, kb, Z)
+        if g > 0:
+            a, b = int(self.base[0, kb]), int(self.base[self.x, kb])
+            lam = [self._row(c, t, kb) for t in range(g)]
+            s = np.bitwise_xor.reduce(lam, axis=0)  # s[r] = p_0[(r + b) % Z]
+            c[:, kb] = np.roll(s, b, axis=1)
+            c[:, kb + 1] = lam[0] ^ np.roll(c[:, kb], -a, axis=1)
+            for t in range(1, g - 1):
+                c[:, kb + t + 1] = lam[t] ^ c[:, kb + t] ^ (s if t == self.x else 0)
+        for i in range(g, self.mb):
+            c[:, kb + i] = np.roll(self._row(c, i, kb + i), int(self.base[i, kb + i]), axis=1)
+        return c.reshape(-1, self.n).astype(int)
+
+    def encode(self, message: np.ndarray) -> np.ndarray:
+        assert len(message) == self.k, f"Message length must be {self.k}"
+        return self.encode_batch(np.asarray(message)[None, :])[0]
+
+    def encode_batch_device(self, messages, out=None):
+        """Codewords for a batch of k-bit messages on the device (pl_ldpc_qc_encode):
+        messages uint8 [B, k] CUDA tensor (unit inner stride, any row pitch; bit 0
+        of each byte) or array; returns a uint8 [B, n] CUDA tensor, `out` if given
+        (unit inner stride, any row pitch >= n; bytes beyond n stay untouched).
+        Runs on torch's current device, where the tensors must live; the native
+        handle is created per device on first use."""
+        import torch
+        from .. import _native
+        msg = messages if isinstance(messages, torch.Tensor) else torch.from_numpy(np.array(messages, dtype=np.uint8))
+        msg = msg.to(device="cuda", dtype=torch.uint8)
+        assert msg.dim() == 2 and msg.shape[1] == self.k, "messages must be [B, k]"
+        if msg.stride(1) != 1 or (msg.shape[0] > 1 and msg.stride(0) < self.k):
+            msg = msg.contiguous()
+        cw = out if out is not None else torch.empty((msg.shape[0], self.n), dtype=torch.uint8, device="cuda")
+        assert cw.is_cuda and cw.dtype == torch.uint8 and cw.shape == (msg.shape[0], self.n) and cw.stride(1) == 1 \
+            and (cw.shape[0] <= 1 or cw.stride(0) >= self.n), "out must be a uint8 [B, n] device tensor, rows apart"
+        dev = torch.cuda.current_device()  # a handle belongs to the device current at its creation
+        if dev not in self._enc:
+            self._enc[dev] = _native.qc_encoder(self.base, self.Z)
+        self._enc[dev].encode(msg, cw)
+        return cw
+
+    def verify_codeword(self, codeword: np.ndarray) -> bool:
+        """H c = 0 over GF(2), block-wise (H is not expanded)."""
+        c = (np.asarray(codeword, dtype=np.int64) & 1).astype(np.uint8).reshape(1, self.nb, self.Z)
+        return not any(self._row(c, i, self.nb).any() for i in range(self.mb))
+
+    def get_code_rate(self) -> float:
+        return self.k / self.n
+
+    def __repr__(self) -> str:
+        return (f"QCLDPCEncoder(n={self.n}, k={self.k}, Z={self.Z}, core={self.g}, "
+                f"rate={self.get_code_rate():.3f})")

@@ -110,6 +110,93 @@ def qc_random_base(mb: int, nb: int, Z: int, dv: int, seed: int) -> np.ndarray:
             return base
 
 
+def qc_encoding_structure(base) -> Tuple[int, Optional[int]]:
+    """(g, x) of a base matrix that QCLDPCEncoder can encode from: the parity part
+    base[:, kb:], kb = nb - mb >= 1, is a core of g block rows (g == 0 or g >= 3)
+    followed by a lower-triangular extension (include/polarldpc.h,
+    pl_ldpc_qc_encoder_create).  x is the middle row of parity column kb, None when
+    g == 0.  ValueError naming the first rule violated for anything else."""
+    base = np.asarray(base)
+    if base.ndim != 2 or base.size == 0:
+        raise ValueError("base must be [mb, nb]")
+    mb, nb = base.shape
+    kb = nb - mb
+    if kb < 1:
+        raise ValueError("kb = nb - mb must be >= 1 (no message block column)")
+    P = base[:, kb:] >= 0
+
+    def ext_ok(i):
+        return bool(P[i, i]) and not P[i, i + 1:].any()
+
+    f = mb - 1
+    while f >= 0 and ext_ok(f):
+        f -= 1
+    if f < 0:
+        return 0, None
+    g = f + 2  # the last row that is no extension row is core row g - 2
+    if g > mb:
+        raise ValueError("block row %d is no extension row (a diagonal block and none to its right) and cannot be "
+                         "the last but one row of a core" % f)
+    if g == 2:
+        raise ValueError("a core of g = 2 block rows: g must be 0 or >= 3")
+    if P[:g, g:].any():
+        i, t = np.argwhere(P[:g, g:])[0]
+        raise ValueError("core block row %d has a block in parity column kb+%d" % (i, g + t))
+    rows = np.nonzero(P[:g, 0])[0]
+    if len(rows) != 3 or rows[0] != 0 or rows[2] != g - 1:
+        raise ValueError("parity column kb+0 must have exactly three blocks in the core, in rows 0, x and g-1 = %d "
+                         "(it has them in rows %s)" % (g - 1, rows.tolist()))
+    x = int(rows[1])
+    if base[0, kb] != base[g - 1, kb]:
+        raise ValueError("the first and the last block of parity column kb+0 must have equal shifts (%d, %d)"
+                         % (base[0, kb], base[g - 1, kb]))
+    for t in range(1, g):
+        rows = np.nonzero(P[:g, t])[0]
+        if rows.tolist() != [t - 1, t]:
+            raise ValueError("parity column kb+%d must have exactly two blocks in the core, in rows %d and %d"
+                             % (t, t - 1, t))
+        if base[t - 1, kb + t] != 0 or base[t, kb + t] != 0:
+            raise ValueError("the dual-diagonal blocks of parity column kb+%d must have shift 0" % t)
+    return g, x
+
+
+def qc_encodable_base(mb: int, nb: int, Z: int, dv: int, seed: int, core: Optional[int] = None,
+                      chained: bool = True) -> np.ndarray:
+    """A seeded random base matrix of the structure qc_encoding_structure accepts,
+    with g = mb (core None) or g = core (0 or 3 .. mb) core rows.  Message columns
+    as qc_random_base; then x in 1 .. g-2 and the shifts (a, b) of parity column
+    kb; then per extension row its diagonal shift and, where an earlier parity
+    column is allowed (any below the diagonal when `chained`, else a core one),
+    one more block there.  chained=False: no extension row reads an extension
+    parity.  The whole matrix is redrawn (the generator continuing) until every
+    block row has at least 2 non-zero blocks."""
+    g = mb if core is None else int(core)
+    kb = nb - mb
+    if kb < 1 or not (g == 0 or 3 <= g <= mb):
+        raise ValueError("needs nb - mb >= 1 and core == 0 or 3 <= core <= mb")
+    rng = np.random.RandomState(seed)
+    while True:
+        base = np.full((mb, nb), -1, dtype=np.int64)
+        for j in range(kb):
+            rows = rng.choice(mb, dv, replace=False)
+            base[rows, j] = rng.randint(0, Z, dv)
+        if g > 0:
+            x = rng.randint(1, g - 1)
+            a, b = rng.randint(0, Z, 2)
+            base[0, kb] = base[g - 1, kb] = a
+            base[x, kb] = b
+            for t in range(1, g):
+                base[t - 1, kb + t] = base[t, kb + t] = 0
+        for i in range(g, mb):
+            base[i, kb + i] = rng.randint(0, Z)
+            lim = i if chained else g
+            if lim > 0:
+                col = kb + rng.randint(0, lim)
+                base[i, col] = rng.randint(0, Z)
+        if np.all((base >= 0).sum(axis=1) >= 2):
+            return base
+
+
 def mackay_construction(n: int, k: int, dv: int, dc: int, seed: Optional[int] = None) -> np.ndarray:
     m = n - k
     if dv * n != dc * m:

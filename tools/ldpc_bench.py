@@ -1,7 +1,8 @@
 """LDPC decode kernel timing (diagnostic): HIP events around repeated launches.
 
 usage: python tools/ldpc_bench.py [--batch 65536] [--algo bp,ms,lms,qclms,qclms32] [--n 504] [--seed 3]
-                                  [--qc mb,nb,Z,dv,seed] [--max-iter 20] [--no-early-stop]
+                                  [--qc mb,nb,Z,dv,seed] [--qc-encodable]
+                                  [--random-codewords] [--max-iter 20] [--no-early-stop]
                                   [--snr 3.0] [--valid] [--norm 0.75] [--reps 5] [--rounds 3]
 
 Default (no --n): the bench's (504,252) MacKay code (seed 42, degree-1 rows: BP
@@ -16,6 +17,11 @@ frames must be equal (asserted).  `qclms32` is QCLayeredMSDecoder(dtype=float32)
 on the same device frames, cast once to fp32 outside the timed region; it is
 another decoder (every operation in binary32), so its results are reported, not
 compared: `frames_differ_from_qclms` counts the frames whose bits differ.
+--qc-encodable: the code qc_encodable_base(mb, nb, Z, dv, seed) instead, whose parity
+part QCLDPCEncoder can encode from; without it --qc means what it always meant.
+--random-codewords (needs --qc-encodable): the frames carry random messages encoded on
+the device by QCLDPCEncoder instead of the all-zero codeword; frame errors are
+counted against those codewords.
 --algo takes a comma-separated list; the decoders are timed alternately on the
 same frames, `rounds` times each, and one JSON line per entry gives the median
 and the spread of the per-launch time.  Each entry may carry its own iteration
@@ -26,8 +32,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from polarcode_and_ldpc_amd.channel import AWGNChannel
 from polarcode_and_ldpc_amd import _native
-from polarcode_and_ldpc_amd.ldpc import (BPDecoder, MSDecoder, LayeredMSDecoder, LDPCEncoder, QCLayeredMSDecoder,
-                                         qc_block_layers, qc_random_base, qc_to_csr, regular_construction)
+from polarcode_and_ldpc_amd.ldpc import (BPDecoder, MSDecoder, LayeredMSDecoder, LDPCEncoder, QCLDPCEncoder,
+                                         QCLayeredMSDecoder, qc_block_layers, qc_encodable_base, qc_random_base,
+                                         qc_to_csr, regular_construction)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=65536)
@@ -40,17 +47,29 @@ ap.add_argument("--norm", type=float, default=0.75, help="min-sum normalisation 
 ap.add_argument("--n", type=int, default=0, help="regular (3,6) code of this length instead of the bench's code")
 ap.add_argument("--seed", type=int, default=3, help="regular_construction seed (--n)")
 ap.add_argument("--qc", default="", help="mb,nb,Z,dv,seed: a qc_random_base code instead (algos lms, qclms)")
+ap.add_argument("--qc-encodable", action="store_true", help="--qc builds qc_encodable_base(mb, nb, Z, dv, seed)")
+ap.add_argument("--random-codewords", action="store_true",
+                help="--qc-encodable: random codewords from QCLDPCEncoder instead of the all-zero one")
 ap.add_argument("--reps", type=int, default=5, help="launches per timed round")
 ap.add_argument("--rounds", type=int, default=3)
 a = ap.parse_args()
 B = a.batch
+if (a.qc_encodable and not a.qc) or (a.random_codewords and not a.qc_encodable):
+    raise SystemExit("--qc-encodable needs --qc mb,nb,Z,dv,seed, and --random-codewords needs --qc-encodable")
 qc = None
 if a.qc:
     mb, nb, Z, dv, qseed = (int(x) for x in a.qc.split(","))
-    qc = qc_random_base(mb, nb, Z, dv, qseed)
+    if a.qc_encodable:
+        qc = qc_encodable_base(mb, nb, Z, dv, qseed)
+    else:
+        qc = qc_random_base(mb, nb, Z, dv, qseed)
     n, k = nb * Z, (nb - mb) * Z
     H = None
     cw = None
+    if a.random_codewords:
+        msg = torch.empty((B, k), dtype=torch.uint8, device="cuda")
+        _native.random_bits(4243, 0, msg)
+        cw = QCLDPCEncoder(qc, Z).encode_batch_device(msg)
 elif a.n:
     n, k = a.n, a.n // 2
     H = regular_construction(n, 3, 6, seed=a.seed)
@@ -123,7 +142,7 @@ for s, d in zip(specs, decs):  # warm-up: plan creation, workspace, first launch
     d._check_runnable()
     d.plan.decode(frames_of(s), out, its)
     torch.cuda.synchronize()
-    wrong = (out != 0).any(dim=1) if cw is None else None
+    wrong = (out != 0).any(dim=1) if cw is None else (out != cw).any(dim=1) if a.random_codewords else None
     stats.append({"mean_iter": float(its.double().mean()),
                   "frame_errors": int(wrong.sum()) if wrong is not None else None})
     if qc is not None:
@@ -152,6 +171,7 @@ for s, d, t, st in zip(specs, decs, times, stats):
     print(json.dumps({"algo": s, "n": n, "batch": B, "early_stop": es, "snr_db": a.snr, "kernel_ms": ms,
                       "kernel_ms_min": min(t), "kernel_ms_max": max(t), "info_mbps": B * k / ms / 1e3,
                       "mean_iter": st["mean_iter"], "frame_errors": st["frame_errors"],
+                      **({"codewords": "random"} if a.random_codewords else {}),
                       "plan_kernel": int(d.plan.info.reserved), "lds_bytes": int(d.plan.info.lds_bytes),
                       **({"frames_differ_from_qclms": st["frames_differ_from_qclms"]}
                          if "frames_differ_from_qclms" in st else {}),
