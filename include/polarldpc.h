@@ -394,13 +394,18 @@ int pl_debug_ldpc_qc_plan_probe_flags(int32_t mb, int32_t nb, int32_t z, const i
  *      message/encode loop of benchmarks/ber_simulation.py:167-177) ---------- */
 
 /* Random message bits, uint8 [batch][k], Philox4x32-10 keyed by (seed, global
- * frame index = frame_offset + b): identical for any sharding of the frames. */
+ * frame index = frame_offset + b): identical for any sharding of the frames.
+ * Counter, key and bit order: DESIGN.md section 4.4, "Stream contract". */
 int pl_random_bits(uint64_t seed, int64_t frame_offset, int64_t batch, int32_t k, uint8_t* bits_dev,
                    void* stream);
 
 /* Polar encoder (src/polar/encoder.py:63-95 without CRC): u[info] = msg,
  * u[frozen] = 0, x = u * F^{(x)n} (src/polar/utils.py:193-229).
- * msg_dev uint8 [batch][K]; codeword_dev uint8 [batch][N]. */
+ * msg_dev uint8 [batch][K] (bit 0 of each byte); codeword_dev uint8 [batch][N].
+ * Index order: DESIGN.md section 4.4, "Stream contract".  Any polar plan encodes,
+ * also one whose decoder geometry needs more LDS than the device has (list_size
+ * 0 or 1 at N = 32768): such a plan is created for encoding only, and every
+ * decode call on it returns PL_EUNSUPPORTED. */
 int pl_polar_encode(const pl_plan* plan, const uint8_t* msg_dev, int64_t batch, uint8_t* codeword_dev,
                     void* stream);
 
@@ -408,19 +413,23 @@ int pl_polar_encode(const pl_plan* plan, const uint8_t* msg_dev, int64_t batch, 
  * (awgn.py:27-32, :47, :88), LLR = 2*y/sigma^2 (:75).  codeword_dev uint8 (bit 0 of each byte)
  * [batch][n] or NULL for the all-zero codeword.  Noise: Philox4x32-10 keyed by
  * (seed, frame_offset + b) + Box-Muller; statistically equivalent to the
- * reference's np.random.normal, not stream-identical. */
+ * reference's np.random.normal, not stream-identical.  Counter, key, uniforms
+ * and the tested error bound: DESIGN.md section 4.4, "Stream contract". */
 int pl_awgn_llr(const uint8_t* codeword_dev, int32_t n, int64_t batch, double snr_db, uint64_t seed,
                 int64_t frame_offset, double* llr_dev, int64_t ld, void* stream);
 
 /* Rayleigh fading + BPSK + AWGN (src/channel/fading.py:31-63): per bit
  * |h| (h complex Gaussian, E|h|^2 = 1), y = |h| s + N(0, sigma), LLR =
  * 2 y |h| / sigma^2, sigma = sqrt(1/(2*10^(snr_db/10))).  Philox keyed by (seed,
- * frame_offset + b, bit); statistically equivalent, not stream-identical. */
+ * frame_offset + b, bit); statistically equivalent, not stream-identical.
+ * Counters, salts and the tested error bound: DESIGN.md section 4.4, "Stream
+ * contract". */
 int pl_rayleigh_llr(const uint8_t* codeword_dev, int32_t n, int64_t batch, double snr_db, uint64_t seed,
                     int64_t frame_offset, double* llr_dev, int64_t ld, void* stream);
 
 /* Binary symmetric channel (src/channel/bsc.py:33-49): out[b][j] = cw[b][j] ^
- * (u < crossover_prob), u uniform per bit; codeword_dev NULL = all-zero word. */
+ * (u < crossover_prob), u uniform per bit; codeword_dev NULL = all-zero word.
+ * Counter, key and u: DESIGN.md section 4.4, "Stream contract". */
 int pl_bsc(const uint8_t* codeword_dev, int32_t n, int64_t batch, double crossover_prob, uint64_t seed,
            int64_t frame_offset, uint8_t* out_dev, int64_t ld, void* stream);
 

@@ -59,6 +59,10 @@ struct pl_plan {
     pl::LaneGeom lgeo{};
     int fpw = 1;            // frames per wavefront
     int lane_grid_max = 0;  // resident wavefronts (persistent grid)
+    // false: the lane kernel's geometry needs more LDS than the device has (SC and
+    // list 1 at N = 32768: 64 frames' final transforms, 256 KiB).  The plan then
+    // serves pl_polar_encode only; decodes return PL_EUNSUPPORTED.
+    bool decodable = true;
     // ldpc
     pl::LdpcGeom lg{};
     pl::LdpcDev ld{};
@@ -99,6 +103,9 @@ static int fail(int code, const std::string& msg) {
     return code;
 }
 static int hipfail(hipError_t e, const char* what) {
+    // the runtime keeps a failed call's code as its "last error": taken here, so that
+    // the caller's next launch (torch checks it after each of its own) does not report it
+    (void)hipGetLastError();
     return fail(e == hipErrorOutOfMemory ? PL_ENOMEM : PL_EHIP,
                 std::string(what) + ": " + hipGetErrorString(e));
 }
@@ -237,7 +244,12 @@ extern "C" int pl_polar_plan_create(int32_t N, int32_t K, const uint8_t* frozen_
         p->pg.lds_bytes = p->lgeo.lds_bytes;
         p->fpw = p->lgeo.lcap >= 64 ? 1 : 64 / p->lgeo.lcap;
         p->ws_unit = (size_t)p->lgeo.ws_bytes;
-        e = pl::lane_prepare(p->lgeo, p->sc, &per_cu);
+        int optin = 0;
+        e = hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, p->device);
+        if (e == hipSuccess) {
+            p->decodable = p->lgeo.lds_bytes <= optin;
+            if (p->decodable) e = pl::lane_prepare(p->lgeo, p->sc, &per_cu);
+        }
     }
     if (e != hipSuccess) {
         pl_plan_destroy(p);
@@ -694,6 +706,9 @@ static int check_decode_args(const pl_plan* p, int64_t batch, int64_t ld, const 
     if (batch > 0 && (!llr || !bits)) return fail(PL_EINVAL, "NULL buffer");
     if (p->kind == 0 && ld < p->pg.N) return fail(PL_EINVAL, "ld < N");
     if (p->kind == 1 && ld < p->lg.n) return fail(PL_EINVAL, "ld < n");
+    if (p->kind == 0 && !p->decodable)
+        return fail(PL_EUNSUPPORTED, "this plan's decoder needs more LDS than the device has (list_size 0 or 1 at "
+                                     "N = 32768): it serves pl_polar_encode only");
     return PL_OK;
 }
 

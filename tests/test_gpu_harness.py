@@ -118,7 +118,8 @@ def test_ldpc_mc_random_codewords_match_zero_codeword(gpu):
 
 @pytest.mark.parametrize("width,ld,off", [(512, 512, 0), (512, 528, 16), (252, 252, 0), (504, 512, 0),
                                           (16, 16, 0), (1024, 1024, 0), (2048, 2048, 0), (8192, 8192, 0),
-                                          (512, 512, 3), (7, 9, 1)])
+                                          (512, 512, 3), (7, 9, 1),
+                                          (48, 48, 0), (1008, 1008, 0), (1040, 1040, 0)])  # 3, 63, 65 chunks
 def test_count_errors_vs_torch(gpu, width, ld, off):
     """pl_count_errors (16-byte chunk paths for aligned rows, byte path otherwise)
     against a torch count of low-bit mismatches; rows with 0, 1 and many errors."""
