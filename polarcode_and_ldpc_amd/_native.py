@@ -233,10 +233,9 @@ class Plan:
         assert isinstance(llr, torch.Tensor) and llr.is_cuda, "llr must be a device tensor"
         if llr.dtype == torch.float32:
             assert self.f32, "fp32 llr: quasi-cyclic plans created with PL_LDPC_QC_F32 only"
-            assert llr.dim() == 2 and llr.stride(1) == 1 and llr.shape[1] >= self.info.n_in
         else:
-            assert llr.dtype == torch.float64 and llr.dim() == 2 and llr.stride(1) == 1 \
-                and llr.shape[1] >= self.info.n_in
+            assert llr.dtype == torch.float64
+        assert llr.dim() == 2 and llr.stride(1) == 1 and llr.shape[1] >= self.info.n_in
         assert bits.is_cuda and bits.dtype == torch.uint8 and bits.shape == (llr.shape[0], self.info.n_out)
         assert bits.is_contiguous(), "bits must be contiguous [B, n_out] (row pitch n_out)"
         if iters is not None:
@@ -249,24 +248,27 @@ class Plan:
         or None; ws: optional caller-owned uint8 device workspace (pl_decode_ws).
         A PL_LDPC_QC_F32 plan also takes fp32 llr (pl_ldpc_decode_f32)."""
         self._check(llr, bits, iters)
-        B = llr.shape[0]
-        it = ctypes.c_void_p(iters.data_ptr()) if iters is not None else None
-        st = ctypes.c_void_p(_stream(stream))
+        assert ws is None or (ws.is_cuda and ws.is_contiguous())
+        self._decode(llr, bits, iters, None, ws, stream)
+
+    def _decode(self, llr, bits, iters, post, ws, stream):
+        """The one call of each decode entry point, arguments already checked: fp32
+        llr -> pl_ldpc_decode_f32 (post and ws optional), fp64 with post ->
+        pl_ldpc_decode_soft, fp64 with ws -> pl_decode_ws, else pl_decode."""
+        # addresses go as plain ints: the argtypes table makes them pointers (0 and None: NULL)
+        head = (self._h, llr.data_ptr(), llr.shape[0], _ld(llr), bits.data_ptr(),
+                iters.data_ptr() if iters is not None else None)
+        soft = (None, 0) if post is None else (post.data_ptr(), _ld(post))
+        work = (None, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())
+        st = _stream(stream)
         if llr.dtype == torch.float32:
-            assert ws is None or (ws.is_cuda and ws.is_contiguous())
-            check(lib.pl_ldpc_decode_f32(self._h, ctypes.c_void_p(llr.data_ptr()), B, _ld(llr),
-                                         ctypes.c_void_p(bits.data_ptr()), it, None, 0,
-                                         None if ws is None else ctypes.c_void_p(ws.data_ptr()),
-                                         0 if ws is None else ws.numel() * ws.element_size(), st),
-                  "pl_ldpc_decode_f32")
-        elif ws is None:
-            check(lib.pl_decode(self._h, ctypes.c_void_p(llr.data_ptr()), B, _ld(llr),
-                                ctypes.c_void_p(bits.data_ptr()), it, st), "pl_decode")
+            check(lib.pl_ldpc_decode_f32(*head, *soft, *work, st), "pl_ldpc_decode_f32")
+        elif post is not None:
+            check(lib.pl_ldpc_decode_soft(*head, *soft, st), "pl_ldpc_decode_soft")
+        elif ws is not None:
+            check(lib.pl_decode_ws(*head, *work, st), "pl_decode_ws")
         else:
-            assert ws.is_cuda and ws.is_contiguous()
-            check(lib.pl_decode_ws(self._h, ctypes.c_void_p(llr.data_ptr()), B, _ld(llr),
-                                   ctypes.c_void_p(bits.data_ptr()), it, ctypes.c_void_p(ws.data_ptr()),
-                                   ws.numel() * ws.element_size(), st), "pl_decode_ws")
+            check(lib.pl_decode(*head, st), "pl_decode")
 
     def decode_soft(self, llr: "torch.Tensor", bits: "torch.Tensor", iters: "torch.Tensor | None",
                     post: "torch.Tensor", stream=None):
@@ -279,16 +281,7 @@ class Plan:
             and post.shape[0] == llr.shape[0] and post.shape[1] >= self.info.n_in, \
             "post must be a [B, >=n] device tensor of llr's dtype (float64; float32 on a PL_LDPC_QC_F32 plan) " \
             "with unit inner stride"
-        it = ctypes.c_void_p(iters.data_ptr()) if iters is not None else None
-        if llr.dtype == torch.float32:
-            check(lib.pl_ldpc_decode_f32(self._h, ctypes.c_void_p(llr.data_ptr()), llr.shape[0], _ld(llr),
-                                         ctypes.c_void_p(bits.data_ptr()), it, ctypes.c_void_p(post.data_ptr()),
-                                         _ld(post), None, 0, ctypes.c_void_p(_stream(stream))),
-                  "pl_ldpc_decode_f32")
-            return
-        check(lib.pl_ldpc_decode_soft(self._h, ctypes.c_void_p(llr.data_ptr()), llr.shape[0], _ld(llr),
-                                      ctypes.c_void_p(bits.data_ptr()), it, ctypes.c_void_p(post.data_ptr()),
-                                      _ld(post), ctypes.c_void_p(_stream(stream))), "pl_ldpc_decode_soft")
+        self._decode(llr, bits, iters, post, None, stream)
 
     def decode_stamped(self, llr: "torch.Tensor", bits: "torch.Tensor", stamps: "torch.Tensor", stream=None):
         """Diagnostic decode accumulating per-phase cycle totals into stamps (int64 [5])."""

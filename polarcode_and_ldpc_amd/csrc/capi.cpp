@@ -32,6 +32,15 @@ struct Workspace {
     // instead of draining and retrying the allocation every call; pl_plan_reserve,
     // or a larger request, retries.
     size_t failed_need = 0;
+    // Wait for the work queued on the buffer's stream (it may still read the buffer), then free
+    // it.  The buffer is gone whatever the wait returns; the caller reports that status.
+    hipError_t drain(hipStream_t s) {
+        const hipError_t e = hipStreamSynchronize(s);
+        hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+        return e;
+    }
     ~Workspace() {
         if (ptr) hipFree(ptr);  // hipFree waits for work that still uses it
     }
@@ -134,14 +143,31 @@ static int env_int(const char* name, int dflt) {
 
 // Every call that touches a plan's device memory must run on the plan's device
 // (the one current at plan creation): a workspace allocated, or a kernel
-// launched, on another device would use foreign pointers.
-static int check_device(const pl_plan* p) {
+// launched, on another device would use foreign pointers.  The same holds for
+// an encoder; `whose`: "plan's" or "encoder's".
+static int check_device(int device, const char* whose) {
     int cur = -1;
     const hipError_t e = hipGetDevice(&cur);
     if (e != hipSuccess) return hipfail(e, "hipGetDevice");
-    if (cur != p->device)
-        return fail(PL_EINVAL, "current device " + std::to_string(cur) + " is not the plan's device " +
-                                   std::to_string(p->device) + " (hipSetDevice first)");
+    if (cur != device)
+        return fail(PL_EINVAL, "current device " + std::to_string(cur) + " is not the " + whose + " device " +
+                                   std::to_string(device) + " (hipSetDevice first)");
+    return PL_OK;
+}
+static int check_device(const pl_plan* p) { return check_device(p->device, "plan's"); }
+
+// A plan or an encoder under construction: destroyed on every return that does not release() it into *out.
+template <class T, int (*Destroy)(T*)>
+struct Destroyer {
+    void operator()(T* t) const { Destroy(t); }
+};
+using PlanPtr = std::unique_ptr<pl_plan, Destroyer<pl_plan, pl_plan_destroy>>;
+
+// fn(b0, nb) on consecutive chunks of at most `step` frames; stops at the first status that is not PL_OK.
+template <class F>
+static int for_chunks(int64_t batch, int64_t step, F&& fn) {
+    for (int64_t b0 = 0; b0 < batch; b0 += step)
+        if (const int rc = fn(b0, std::min<int64_t>(step, batch - b0))) return rc;
     return PL_OK;
 }
 
@@ -179,7 +205,8 @@ extern "C" int pl_polar_plan_create(int32_t N, int32_t K, const uint8_t* frozen_
     for (int i = 0; i < N; ++i)
         if (frozen_mask[bitrev(i, n)]) fdec[i >> 5] |= 1u << (i & 31);
 
-    pl_plan* p = new pl_plan();
+    PlanPtr plan(new pl_plan());
+    pl_plan* const p = plan.get();
     p->kind = 0;
     p->h_info = info;
     p->sc = (list_size == 0);
@@ -194,10 +221,8 @@ extern "C" int pl_polar_plan_create(int32_t N, int32_t K, const uint8_t* frozen_
     p->tree = !p->generic && !(kern && std::string(kern) == "lane") && !(flags & 0x3F) &&
               pl::tree_lookup(n, lcap, p->sc, &p->tinfo);
     hipError_t e;
-    if ((e = upload(&p->d_frozen_dec, fdec)) != hipSuccess || (e = upload(&p->d_info_pos, info)) != hipSuccess) {
-        pl_plan_destroy(p);
+    if ((e = upload(&p->d_frozen_dec, fdec)) != hipSuccess || (e = upload(&p->d_info_pos, info)) != hipSuccess)
         return hipfail(e, "plan upload");
-    }
     p->pg.N = N;
     p->pg.K = K;
     if (p->tree && p->sc) {
@@ -216,10 +241,8 @@ extern "C" int pl_polar_plan_create(int32_t N, int32_t K, const uint8_t* frozen_
             }
             r0k[(size_t)i >> 3] |= (uint32_t)k << (4 * (i & 7));
         }
-        if ((e = upload(&p->d_r0k, r0k)) != hipSuccess) {
-            pl_plan_destroy(p);
+        if ((e = upload(&p->d_r0k, r0k)) != hipSuccess)
             return hipfail(e, "plan upload");
-        }
     }
     int per_cu = 1;
     if (p->generic) {
@@ -251,10 +274,8 @@ extern "C" int pl_polar_plan_create(int32_t N, int32_t K, const uint8_t* frozen_
             if (p->decodable) e = pl::lane_prepare(p->lgeo, p->sc, &per_cu);
         }
     }
-    if (e != hipSuccess) {
-        pl_plan_destroy(p);
+    if (e != hipSuccess)
         return hipfail(e, "polar kernel prepare");
-    }
     p->lane_grid_max = per_cu * device_cus(p->device);
     const int waves_env = env_int("PL_POLAR_WAVES", 0);
     if (waves_env > 0) p->lane_grid_max = waves_env;
@@ -262,10 +283,8 @@ extern "C" int pl_polar_plan_create(int32_t N, int32_t K, const uint8_t* frozen_
         p->tinfo_small.ws_bytes <= p->tinfo.ws_bytes && p->tinfo_small.fpw == p->fpw) {
         // its slices fit the main instance's (the workspace is sized for that one)
         int per_cu_small = 0;
-        if ((e = pl::tree_prepare(p->tinfo_small, &per_cu_small)) != hipSuccess) {
-            pl_plan_destroy(p);
+        if ((e = pl::tree_prepare(p->tinfo_small, &per_cu_small)) != hipSuccess)
             return hipfail(e, "polar kernel prepare");
-        }
         p->small_grid_max = std::min(per_cu_small * device_cus(p->device), p->lane_grid_max);
         p->tree_small = p->small_grid_max > 0;
     }
@@ -276,10 +295,8 @@ extern "C" int pl_polar_plan_create(int32_t N, int32_t K, const uint8_t* frozen_
         if (p->generic) {  // scratch of up to 2 GB (at least one frame's): a 2048-path list of N = 1024 holds 23 MB
             // one frame's list state must fit the device (list_size * N = 2^30 needs ~11 GB)
             size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && p->redo_unit > total_b) {
-                pl_plan_destroy(p);
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && p->redo_unit > total_b)
                 return fail(PL_EUNSUPPORTED, "list_size: one frame's list state exceeds this device's memory");
-            }
             const size_t cap = (size_t)2 << 30;
             p->redo_blocks = (int)std::max<size_t>(1, std::min<size_t>((size_t)p->redo_blocks, cap / p->redo_unit));
             p->lane_grid_max = p->redo_blocks;
@@ -288,21 +305,15 @@ extern "C" int pl_polar_plan_create(int32_t N, int32_t K, const uint8_t* frozen_
         // a list whose state does not fit the device's LDS is refused here, so that any error
         // of the prepare call itself is a HIP error
         int optin = 0;
-        if ((e = hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, p->device)) != hipSuccess) {
-            pl_plan_destroy(p);
+        if ((e = hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, p->device)) != hipSuccess)
             return hipfail(e, "device attribute query");
-        }
-        if (pl::nan_redo_lds_bytes(list_size) > optin) {
-            pl_plan_destroy(p);
+        if (pl::nan_redo_lds_bytes(list_size) > optin)
             return fail(PL_EUNSUPPORTED, "list_size: the redo kernel's list state exceeds this device's LDS");
-        }
-        if ((e = pl::nan_redo_prepare(list_size)) != hipSuccess) {
-            pl_plan_destroy(p);
+        if ((e = pl::nan_redo_prepare(list_size)) != hipSuccess)
             return hipfail(e, "NaN redo kernel prepare");
-        }
     }
     p->head_bytes = p->mask_bytes + (p->generic ? 0 : (size_t)pl::kSchedBytes);
-    *out = p;
+    *out = plan.release();
     return PL_OK;
 }
 
@@ -331,15 +342,14 @@ static pl::LdpcPlanOptions ldpc_env_options() {
 }
 
 // An LDPC plan object around the planner's tables, uploaded as one device buffer.
-static int ldpc_plan_upload(const std::vector<int32_t>& tables, pl_plan** p) {
-    *p = new pl_plan();
-    (*p)->kind = 1;
-    hipGetDevice(&(*p)->device);
-    (*p)->ldpc_chunk = std::max(1, env_int("PL_LDPC_CHUNK", 16384));
-    const hipError_t e = upload(&(*p)->d_ldpc, tables);
-    if (e == hipSuccess) return PL_OK;
-    pl_plan_destroy(*p);
-    return hipfail(e, "plan upload");
+static int ldpc_plan_upload(const std::vector<int32_t>& tables, PlanPtr* plan) {
+    pl_plan* const p = new pl_plan();
+    plan->reset(p);
+    p->kind = 1;
+    hipGetDevice(&p->device);
+    p->ldpc_chunk = std::max(1, env_int("PL_LDPC_CHUNK", 16384));
+    const hipError_t e = upload(&p->d_ldpc, tables);
+    return e == hipSuccess ? PL_OK : hipfail(e, "plan upload");
 }
 
 extern "C" int pl_ldpc_plan_create(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
@@ -353,14 +363,15 @@ extern "C" int pl_ldpc_plan_create(int32_t m, int32_t n, const int32_t* row_ptr,
     const pl::PlanStatus st =
         pl::ldpc_plan_build(m, n, row_ptr, col_idx, algo, max_iter, early_stop, normalization, ldpc_env_options(), &hp);
     if (st.code) return fail(st.code, st.msg);
-    pl_plan* p;
-    if (int rc = ldpc_plan_upload(hp.tables, &p)) return rc;
+    PlanPtr plan;
+    if (int rc = ldpc_plan_upload(hp.tables, &plan)) return rc;
+    pl_plan* const p = plan.get();
     p->lg = hp.geom;
     p->ld = hp.dev(p->d_ldpc);
     const hipError_t e = pl::ldpc_prepare(p->lg);
-    if (e != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "hipFuncSetAttribute"); }
+    if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute");
     p->ws_unit = pl::ldpc_work_bytes_per_frame(p->lg);
-    *out = p;
+    *out = plan.release();
     return PL_OK;
 }
 
@@ -376,16 +387,17 @@ extern "C" int pl_ldpc_layered_plan_create(int32_t m, int32_t n, const int32_t* 
     const pl::PlanStatus st = pl::lms_plan_build(m, n, row_ptr, col_idx, n_layers, layer_ptr, layer_rows, max_iter,
                                                  early_stop, normalization, ldpc_env_options(), &hp);
     if (st.code) return fail(st.code, st.msg);
-    pl_plan* p;
-    if (int rc = ldpc_plan_upload(hp.tables, &p)) return rc;
+    PlanPtr plan;
+    if (int rc = ldpc_plan_upload(hp.tables, &plan)) return rc;
+    pl_plan* const p = plan.get();
     p->layered = true;
     p->lg.n = n; p->lg.m = m; p->lg.E = hp.geom.E;
     p->lms = hp.geom;
     p->lmsd = hp.dev(p->d_ldpc);
     const hipError_t e = pl::lms_prepare(p->lms);
-    if (e != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "hipFuncSetAttribute"); }
+    if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute");
     p->ws_unit = p->lms.use_global ? (size_t)p->lms.state_bytes : 0;
-    *out = p;
+    *out = plan.release();
     return PL_OK;
 }
 
@@ -401,8 +413,9 @@ extern "C" int pl_ldpc_qc_plan_create(int32_t mb, int32_t nb, int32_t z, const i
     const pl::PlanStatus st = pl::qc_plan_build(mb, nb, z, shift, layer_order, max_iter, early_stop, normalization,
                                                 opt, &hp);
     if (st.code) return fail(st.code, st.msg);
-    pl_plan* p;
-    if (int rc = ldpc_plan_upload(hp.tables, &p)) return rc;
+    PlanPtr plan;
+    if (int rc = ldpc_plan_upload(hp.tables, &plan)) return rc;
+    pl_plan* const p = plan.get();
     p->layered = true;
     p->qc = true;
     p->qcg = hp.geom;
@@ -410,9 +423,9 @@ extern "C" int pl_ldpc_qc_plan_create(int32_t mb, int32_t nb, int32_t z, const i
     p->lg.n = p->lms.n = hp.geom.n;
     p->lg.m = p->lms.m = hp.geom.m;
     const hipError_t e = pl::qc_prepare(p->qcg, p->qc_f32);
-    if (e != hipSuccess) { pl_plan_destroy(p); return hipfail(e, "hipFuncSetAttribute"); }
+    if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute");
     p->ws_unit = p->qcg.use_global ? (size_t)p->qcg.state_bytes : 0;
-    *out = p;
+    *out = plan.release();
     return PL_OK;
 }
 
@@ -525,8 +538,7 @@ static int lms_decode_impl(pl_plan* p, const IO* llr, int64_t batch, int64_t ld,
         return fail(PL_EINVAL, "workspace smaller than one unit (pl_plan_workspace_bytes)");
     const int64_t step = p->ws_unit > 0 ? std::min<int64_t>(p->ldpc_chunk, (int64_t)(ws_bytes / p->ws_unit))
                                         : kMaxLaunchItems / 1024;
-    for (int64_t b0 = 0; b0 < batch; b0 += step) {
-        const int64_t nb = std::min<int64_t>(step, batch - b0);
+    return for_chunks(batch, step, [&](int64_t b0, int64_t nb) {
         uint8_t* const bo = bits + b0 * p->lms.n;
         int32_t* const io = iters ? iters + b0 : nullptr;
         IO* const po = post ? post + b0 * ld_post : nullptr;
@@ -539,9 +551,8 @@ static int lms_decode_impl(pl_plan* p, const IO* llr, int64_t batch, int64_t ld,
         } else {
             e = pl::qc_launch(p->qcg, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb, (unsigned char*)ws, s);
         }
-        if (e != hipSuccess) return hipfail(e, "layered ldpc decode launch");
-    }
-    return PL_OK;
+        return e == hipSuccess ? PL_OK : hipfail(e, "layered ldpc decode launch");
+    });
 }
 
 // Decode with an explicit workspace of ws_bytes (>= one unit when one is needed):
@@ -578,7 +589,8 @@ static int decode_impl(pl_plan* p, const double* llr, int64_t batch, int64_t ld,
             hipError_t e = hipMemsetAsync(masks, 0, (size_t)grid * 8 * pl::kNanMaskPasses, s);
             if (e != hipSuccess) return hipfail(e, "NaN mask reset");
         }
-        // a list launch runs at most kNanMaskPasses passes of its grid (the masks' depth)
+        // a list launch runs at most kNanMaskPasses passes of its grid (the masks' depth).  Three
+        // steps per chunk, each with its own error, and a readback: a loop of its own, not for_chunks
         const int64_t step = masks ? grid * p->fpw * pl::kNanMaskPasses : batch;
         for (int64_t b0 = 0; b0 < batch; b0 += step) {
             const int64_t nb = std::min<int64_t>(step, batch - b0);
@@ -617,25 +629,16 @@ static int decode_impl(pl_plan* p, const double* llr, int64_t batch, int64_t ld,
         }
         return PL_OK;
     }
-    if (!p->lg.use_global) {
-        // one workgroup per frame; HIP caps a grid at 2^32 work-items
-        const int64_t step = kMaxLaunchItems / p->lg.threads;
-        for (int64_t b0 = 0; b0 < batch; b0 += step) {
-            const int64_t nb = std::min<int64_t>(step, batch - b0);
-            hipError_t e = pl::ldpc_launch(p->lg, p->ld, llr + b0 * ld, ld, bits + b0 * p->lg.n,
-                                           iters ? iters + b0 : nullptr, nb, nullptr, s);
-            if (e != hipSuccess) return hipfail(e, "ldpc decode launch");
-        }
-        return PL_OK;
-    }
-    const int64_t chunk = std::min<int64_t>(p->ldpc_chunk, (int64_t)(ws_bytes / p->ws_unit));
-    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-        const int64_t nb = std::min<int64_t>(chunk, batch - b0);
-        hipError_t e = pl::ldpc_launch(p->lg, p->ld, llr + b0 * ld, ld, bits + b0 * p->lg.n,
-                                       iters ? iters + b0 : nullptr, nb, (double*)ws, s);
-        if (e != hipSuccess) return hipfail(e, "ldpc decode launch");
-    }
-    return PL_OK;
+    // Flooding LDPC, one workgroup per frame.  Messages in LDS: no workspace, and HIP caps a grid at
+    // 2^32 work-items; messages in the workspace: chunks of the frames it holds.
+    const int64_t step = p->lg.use_global ? std::min<int64_t>(p->ldpc_chunk, (int64_t)(ws_bytes / p->ws_unit))
+                                          : kMaxLaunchItems / p->lg.threads;
+    double* const work = p->lg.use_global ? (double*)ws : nullptr;
+    return for_chunks(batch, step, [&](int64_t b0, int64_t nb) {
+        const hipError_t e = pl::ldpc_launch(p->lg, p->ld, llr + b0 * ld, ld, bits + b0 * p->lg.n,
+                                             iters ? iters + b0 : nullptr, nb, work, s);
+        return e == hipSuccess ? PL_OK : hipfail(e, "ldpc decode launch");
+    });
 }
 
 // The calling stream's workspace entry (created empty on first use).
@@ -664,10 +667,7 @@ static int grow_ws(pl_plan* p, Workspace* w, hipStream_t s, size_t need, bool re
         if (e == hipSuccess) {
             if (w->ptr) {
                 // the old buffer may still be read by work queued on this stream
-                hipError_t se = hipStreamSynchronize(s);
-                hipFree(w->ptr);
-                w->ptr = nullptr;
-                w->bytes = 0;
+                const hipError_t se = w->drain(s);
                 if (se != hipSuccess) {
                     hipFree(np);
                     return hipfail(se, "workspace regrow: stream synchronize");
@@ -688,16 +688,36 @@ static int grow_ws(pl_plan* p, Workspace* w, hipStream_t s, size_t need, bool re
         (void)hipGetLastError();  // clear the sticky allocation error before retrying
         if (e != hipErrorOutOfMemory) return hipfail(e, "decode workspace");
         if (w->ptr) {  // make room: drain this stream, release its buffer, retry the same size
-            hipError_t se = hipStreamSynchronize(s);
-            hipFree(w->ptr);
-            w->ptr = nullptr;
-            w->bytes = 0;
+            const hipError_t se = w->drain(s);
             if (se != hipSuccess) return hipfail(se, "workspace regrow: stream synchronize");
             continue;
         }
         if (want <= unit) return hipfail(e, "decode workspace");
         want = std::max(unit, (want / 2) / unit * unit);
     }
+}
+
+// run(ws, bytes) on the calling stream's workspace, grown to `need` bytes (less after an
+// out-of-memory fallback: `bytes` is what there is) and held locked for the whole call.
+// need == 0: run(nullptr, 0) with no map entry made, so pl_plan_workspace_stats counts only
+// streams that hold a buffer.  (A polar plan's need is never 0 for batch > 0 -- polar_bytes always
+// includes a slice or redo_unit -- so its diagnostic decodes always take the entry, as they did
+// when they took it unconditionally.)
+template <class F>
+static int with_stream_ws(pl_plan* p, hipStream_t s, size_t need, F&& run) {
+    if (need == 0) return run(nullptr, (size_t)0);
+    const std::shared_ptr<Workspace> w = stream_entry(p, s);
+    std::lock_guard<std::mutex> lk(w->mu);
+    if (const int rc = grow_ws(p, w.get(), s, need, false)) return rc;
+    return run(w->ptr, (size_t)w->bytes);
+}
+
+// pl_decode and the diagnostic decodes: decode_impl on the calling stream's workspace
+static int decode_on_stream(pl_plan* p, const double* llr, int64_t batch, int64_t ld, uint8_t* bits, int32_t* iters,
+                            hipStream_t s, const DecodeDiag& dg = DecodeDiag()) {
+    return with_stream_ws(p, s, ws_need(p, batch), [&](void* ws, size_t bytes) {
+        return decode_impl(p, llr, batch, ld, bits, iters, ws, bytes, s, false, dg);
+    });
 }
 
 static int check_decode_args(const pl_plan* p, int64_t batch, int64_t ld, const void* llr, const void* bits) {
@@ -740,10 +760,7 @@ extern "C" int pl_plan_release(pl_plan* p, void* stream) {
     }
     std::lock_guard<std::mutex> lk(w->mu);  // a decode in flight on this stream finishes its launch first
     if (w->ptr) {
-        hipError_t e = hipStreamSynchronize(s);
-        hipFree(w->ptr);
-        w->ptr = nullptr;
-        w->bytes = 0;
+        const hipError_t e = w->drain(s);
         if (e != hipSuccess) return hipfail(e, "workspace release: stream synchronize");
     }
     return PL_OK;
@@ -773,13 +790,7 @@ extern "C" int pl_decode(pl_plan* p, const double* llr, int64_t batch, int64_t l
     int rc = check_decode_args(p, batch, ld, llr, bits);
     if (rc || batch == 0) return rc;
     if ((rc = check_device(p))) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    const size_t need = ws_need(p, batch);
-    if (!need) return decode_impl(p, llr, batch, ld, bits, iters, nullptr, 0, s);
-    std::shared_ptr<Workspace> w = stream_entry(p, s);
-    std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = grow_ws(p, w.get(), s, need, false))) return rc;
-    return decode_impl(p, llr, batch, ld, bits, iters, w->ptr, w->bytes, s);
+    return decode_on_stream(p, llr, batch, ld, bits, iters, (hipStream_t)stream);
 }
 
 extern "C" int pl_decode_ws(pl_plan* p, const double* llr, int64_t batch, int64_t ld, uint8_t* bits,
@@ -803,12 +814,9 @@ extern "C" int pl_ldpc_decode_soft(pl_plan* p, const double* llr, int64_t batch,
     if (batch == 0) return PL_OK;
     if ((rc = check_device(p))) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    const size_t need = ws_need(p, batch);
-    if (!need) return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, nullptr, 0, s);
-    std::shared_ptr<Workspace> w = stream_entry(p, s);
-    std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = grow_ws(p, w.get(), s, need, false))) return rc;
-    return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, w->ptr, w->bytes, s);
+    return with_stream_ws(p, s, ws_need(p, batch), [&](void* ws, size_t bytes) {
+        return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, ws, bytes, s);
+    });
 }
 
 extern "C" int pl_ldpc_decode_f32(pl_plan* p, const float* llr, int64_t batch, int64_t ld, uint8_t* bits,
@@ -826,12 +834,9 @@ extern "C" int pl_ldpc_decode_f32(pl_plan* p, const float* llr, int64_t batch, i
     const hipStream_t s = (hipStream_t)stream;
     if (workspace)
         return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, workspace, (size_t)workspace_bytes, s);
-    const size_t need = ws_need(p, batch);
-    if (!need) return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, nullptr, 0, s);
-    std::shared_ptr<Workspace> w = stream_entry(p, s);
-    std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = grow_ws(p, w.get(), s, need, false))) return rc;
-    return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, w->ptr, w->bytes, s);
+    return with_stream_ws(p, s, ws_need(p, batch), [&](void* ws, size_t bytes) {
+        return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, ws, bytes, s);
+    });
 }
 
 extern "C" int pl_debug_polar_stamps(pl_plan* p, const double* llr, int64_t batch, int64_t ld, uint8_t* bits,
@@ -844,13 +849,9 @@ extern "C" int pl_debug_polar_stamps(pl_plan* p, const double* llr, int64_t batc
     int rc = check_decode_args(p, batch, ld, llr, bits);
     if (rc || batch == 0) return rc;
     if ((rc = check_device(p))) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    std::shared_ptr<Workspace> w = stream_entry(p, s);
-    std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = grow_ws(p, w.get(), s, ws_need(p, batch), false))) return rc;
     DecodeDiag dg;
     dg.stamps = stamps_dev;
-    return decode_impl(p, llr, batch, ld, bits, nullptr, w->ptr, w->bytes, s, false, dg);
+    return decode_on_stream(p, llr, batch, ld, bits, nullptr, (hipStream_t)stream, dg);
 #endif
 }
 
@@ -865,14 +866,10 @@ extern "C" int pl_debug_polar_deadstore(pl_plan* p, const double* llr, int64_t b
     if (rc || batch == 0) return rc;
     if ((rc = check_device(p))) return rc;
     if (!p->tree || !p->tinfo.fn_ds[0]) return fail(PL_EUNSUPPORTED, "dead-store instances: N=1024 L=8 tree plans only");
-    const hipStream_t s = (hipStream_t)stream;
-    std::shared_ptr<Workspace> w = stream_entry(p, s);
-    std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = grow_ws(p, w.get(), s, ws_need(p, batch), false))) return rc;
     DecodeDiag dg;
     dg.stamps = reinterpret_cast<unsigned long long*>(mask_dev);
     dg.ds_mode = mode;
-    return decode_impl(p, llr, batch, ld, bits, nullptr, w->ptr, w->bytes, s, false, dg);
+    return decode_on_stream(p, llr, batch, ld, bits, nullptr, (hipStream_t)stream, dg);
 #endif
 }
 
@@ -891,13 +888,9 @@ extern "C" int pl_debug_polar_flagged(pl_plan* p, const double* llr, int64_t bat
     if ((rc = check_device(p))) return rc;
     if (p->generic || p->mask_bytes == 0) return fail(PL_EUNSUPPORTED, "plan has no NaN masks (SC or generic list plan)");
     std::memset(flagged_host, 0, (size_t)batch);
-    const hipStream_t s = (hipStream_t)stream;
-    std::shared_ptr<Workspace> w = stream_entry(p, s);
-    std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = grow_ws(p, w.get(), s, ws_need(p, batch), false))) return rc;
     DecodeDiag dg;
     dg.flagged = flagged_host;
-    return decode_impl(p, llr, batch, ld, bits, nullptr, w->ptr, w->bytes, s, false, dg);
+    return decode_on_stream(p, llr, batch, ld, bits, nullptr, (hipStream_t)stream, dg);
 #endif
 }
 
@@ -1030,13 +1023,11 @@ extern "C" int pl_polar_encode(const pl_plan* p, const uint8_t* msg, int64_t bat
     if (batch < 0 || (batch > 0 && (!msg || !cw))) return fail(PL_EINVAL, "bad argument");
     if (int rc = check_device(p)) return rc;
     const int64_t step = kMaxLaunchItems / 64;  // one wavefront per frame
-    for (int64_t b0 = 0; b0 < batch; b0 += step) {
-        const int64_t nb = std::min<int64_t>(step, batch - b0);
-        hipError_t e = pl::polar_encode_launch(p->pg.N, p->pg.K, p->d_info_pos, msg + b0 * p->pg.K, nb,
-                                               cw + b0 * p->pg.N, (hipStream_t)stream);
-        if (e != hipSuccess) return hipfail(e, "polar encode launch");
-    }
-    return PL_OK;
+    return for_chunks(batch, step, [&](int64_t b0, int64_t nb) {
+        const hipError_t e = pl::polar_encode_launch(p->pg.N, p->pg.K, p->d_info_pos, msg + b0 * p->pg.K, nb,
+                                                     cw + b0 * p->pg.N, (hipStream_t)stream);
+        return e == hipSuccess ? PL_OK : hipfail(e, "polar encode launch");
+    });
 }
 
 extern "C" int pl_awgn_llr(const uint8_t* cw, int32_t n, int64_t batch, double snr_db, uint64_t seed,
@@ -1082,13 +1073,11 @@ extern "C" int pl_gf2_encode(const uint32_t* g_dev, int32_t k, int32_t n, const 
     if (batch < 0 || k < 1 || n < 1 || ld_msg < k || ld_cw < n || (batch > 0 && (!g_dev || !msg || !cw)))
         return fail(PL_EINVAL, "bad argument");
     const int64_t step = kMaxLaunchItems / 64;  // one wavefront per frame
-    for (int64_t b0 = 0; b0 < batch; b0 += step) {
-        const int64_t nb = std::min<int64_t>(step, batch - b0);
-        hipError_t e = pl::gf2_encode_launch(g_dev, k, n, msg + b0 * ld_msg, ld_msg, nb, cw + b0 * ld_cw, ld_cw,
-                                             (hipStream_t)stream);
-        if (e != hipSuccess) return hipfail(e, "gf2 encode launch");
-    }
-    return PL_OK;
+    return for_chunks(batch, step, [&](int64_t b0, int64_t nb) {
+        const hipError_t e = pl::gf2_encode_launch(g_dev, k, n, msg + b0 * ld_msg, ld_msg, nb, cw + b0 * ld_cw, ld_cw,
+                                                   (hipStream_t)stream);
+        return e == hipSuccess ? PL_OK : hipfail(e, "gf2 encode launch");
+    });
 }
 
 // ---- quasi-cyclic encoder from the base matrix (ldpc_qc_encode.hip) ----
@@ -1109,16 +1098,13 @@ extern "C" int pl_ldpc_qc_encoder_create(int32_t mb, int32_t nb, int32_t z, cons
     int dev = -1;
     const hipError_t ge = hipGetDevice(&dev);
     if (ge != hipSuccess) return hipfail(ge, "hipGetDevice");
-    pl_qc_encoder* e = new pl_qc_encoder();
+    std::unique_ptr<pl_qc_encoder, Destroyer<pl_qc_encoder, pl_ldpc_qc_encoder_destroy>> e(new pl_qc_encoder());
     e->g = hp.geom;
     e->device = dev;
     hipError_t err = upload(&e->d_tab, hp.tables);
     if (err == hipSuccess) err = pl::qc_encode_prepare(e->g);
-    if (err != hipSuccess) {
-        pl_ldpc_qc_encoder_destroy(e);
-        return hipfail(err, "encoder upload");
-    }
-    *out = e;
+    if (err != hipSuccess) return hipfail(err, "encoder upload");
+    *out = e.release();
     return PL_OK;
 }
 
@@ -1129,21 +1115,14 @@ extern "C" int pl_ldpc_qc_encode(const pl_qc_encoder* enc, const uint8_t* msg, i
     if (batch < 0) return fail(PL_EINVAL, "batch must be >= 0");
     if (ld_msg < enc->g.k) return fail(PL_EINVAL, "ld_msg < k = " + std::to_string(enc->g.k));
     if (ld_cw < enc->g.n) return fail(PL_EINVAL, "ld_cw < n = " + std::to_string(enc->g.n));
-    int cur = -1;
-    const hipError_t ge = hipGetDevice(&cur);
-    if (ge != hipSuccess) return hipfail(ge, "hipGetDevice");
-    if (cur != enc->device)
-        return fail(PL_EINVAL, "current device " + std::to_string(cur) + " is not the encoder's device " +
-                                   std::to_string(enc->device) + " (hipSetDevice first)");
+    if (int rc = check_device(enc->device, "encoder's")) return rc;
     // whole workgroups per launch, below kMaxLaunchItems work-items
     const int64_t step = kMaxLaunchItems / enc->g.threads * ((int64_t)enc->g.fpw * enc->g.fpb);
-    for (int64_t b0 = 0; b0 < batch; b0 += step) {
-        const int64_t nb = std::min<int64_t>(step, batch - b0);
+    return for_chunks(batch, step, [&](int64_t b0, int64_t nb) {
         const hipError_t e = pl::qc_encode_launch(enc->g, enc->d_tab, msg + b0 * ld_msg, ld_msg, nb, cw + b0 * ld_cw,
                                                   ld_cw, (hipStream_t)stream);
-        if (e != hipSuccess) return hipfail(e, "qc encode launch");
-    }
-    return PL_OK;
+        return e == hipSuccess ? PL_OK : hipfail(e, "qc encode launch");
+    });
 }
 
 extern "C" int pl_ldpc_qc_encoder_destroy(pl_qc_encoder* enc) {

@@ -17,6 +17,8 @@ import torch
 from .. import _native
 from .matrix import dense_to_csr, layer_schedule, qc_block_layers, qc_expand
 
+_TORCH = {np.float64: torch.float64, np.float32: torch.float32}
+
 
 class _LdpcBase:
     _algo = _native.PL_LDPC_BP
@@ -40,37 +42,84 @@ class _LdpcBase:
                                            self.early_stop, self.normalization)
         return self._plan
 
+    # What a subclass may change about decode_batch, which has this one body:
+    _elem = np.float64  # element type of the decoder's state, host LLRs and posteriors
+    _soft_output = False  # decode_batch(return_llr=True) exists: the layered classes
+    # The layered classes write the bits into a host `out` and check runnability on an empty host
+    # batch; the flooding ones (BP, MS) do neither.  Nobody chose the difference; it is kept.
+    _host_out = False
+
     def _check_runnable(self):
         pass
 
-    def _run(self, llr, out=None, iters=None):
-        """Device batch: llr fp64 [B, n] -> (bits uint8 [B, n], iters int32 [B])."""
-        self._check_runnable()
-        B = llr.shape[0]
-        if out is None:
-            out = torch.empty((B, self.n), dtype=torch.uint8, device=llr.device)
-        if iters is None:
-            iters = torch.empty((B,), dtype=torch.int32, device=llr.device)
-        if B > 0:
-            self.plan.decode(llr, out, iters)
-        return out, iters
+    def _device_llr(self, llr):
+        """A CUDA [B, n] tensor as the kernels read it: fp64, unit inner stride, any row pitch."""
+        if llr.dtype != torch.float64 or llr.stride(1) != 1:
+            llr = llr.to(torch.float64).contiguous()
+        return llr
 
-    def decode_batch(self, llr, out: Optional[torch.Tensor] = None, return_iterations: bool = False):
+    def _host_llr(self, llr):
+        return np.asarray(llr, dtype=np.float64)
+
+    def _run(self, llr, out=None, soft=False):
+        """Device batch, no host copy and no synchronise: llr [B, >=n] as _device_llr
+        leaves it -> (bits uint8 [B, n], iters int32 [B], posterior [B, n] or None)."""
+        self._check_runnable()  # deliberate: an empty device batch is checked too
+        B, dev = llr.shape[0], llr.device
+        if out is None:
+            out = torch.empty((B, self.n), dtype=torch.uint8, device=dev)
+        # deliberate: allocated, and handed to the kernel, whether the caller asked for iterations or not
+        iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        post = torch.empty((B, self.n), dtype=_TORCH[self._elem], device=dev) if soft else None
+        if B == 0:
+            pass  # deliberate: no library call, not even the plan's creation
+        elif post is None:
+            self.plan.decode(llr, out, iters)
+        else:
+            # a float32 decoder given fp64 LLRs: the fp64-I/O instance writes the float32 posteriors
+            # widened to an fp64 buffer, which rounds back exactly (the class docstring)
+            wide = post if post.dtype == llr.dtype else torch.empty((B, self.n), dtype=llr.dtype, device=dev)
+            self.plan.decode_soft(llr, out, iters, wide)
+            if wide is not post:
+                post.copy_(wide)
+        return out, iters, post
+
+    def decode_batch(self, llr, out: Optional[torch.Tensor] = None, return_iterations: bool = False,
+                     return_llr: bool = False):
+        """Bits [B, n]; with return_iterations / return_llr (the layered classes
+        only) also the iteration counts and the posterior LLRs, in the order bits,
+        iterations, posterior.  A CUDA tensor in gives CUDA tensors out (no host
+        copy; `out`: a uint8 [B, n] device tensor for the bits); NumPy in gives
+        int64 / float NumPy out (`out`, layered classes only: an int64 [B, n]
+        array for the bits)."""
+        if return_llr and not self._soft_output:
+            raise TypeError("decode_batch() got an unexpected keyword argument 'return_llr'")
+
+        def pick(bits, its, post):  # deliberate: a bare array, not a 1-tuple, when only the bits are asked for
+            r = (bits,) + ((its,) if return_iterations else ()) + ((post,) if return_llr else ())
+            return r if len(r) > 1 else bits
+
         if isinstance(llr, torch.Tensor) and llr.is_cuda:
             assert llr.dim() == 2 and llr.shape[1] == self.n, "LLR length must be %d" % self.n
-            if llr.dtype != torch.float64 or llr.stride(1) != 1:
-                llr = llr.to(torch.float64).contiguous()
-            bits, its = self._run(llr, out)
-            return (bits, its) if return_iterations else bits
-        a = np.asarray(llr.cpu().numpy() if isinstance(llr, torch.Tensor) else llr, dtype=np.float64)
+            return pick(*self._run(self._device_llr(llr), out, return_llr))
+        a = self._host_llr(llr.cpu().numpy() if isinstance(llr, torch.Tensor) else llr)
         assert a.ndim == 2 and a.shape[1] == self.n, "LLR length must be %d" % self.n
+        if not self._host_out:
+            out = None  # deliberate (BP, MS): a host `out` is ignored, a fresh int64 array comes back
         if a.shape[0] == 0:
-            z = np.zeros((0, self.n), dtype=np.int64)
-            return (z, np.zeros(0, dtype=np.int64)) if return_iterations else z
+            if self._host_out:
+                self._check_runnable()  # deliberate: BP / MS return the empty result unchecked
+            bits = np.zeros((0, self.n), dtype=np.int64) if out is None else out  # deliberate: `out` itself
+            return pick(bits, np.zeros(0, dtype=np.int64), np.zeros((0, self.n), dtype=self._elem))
         _native.require_gpu()
-        bits, its = self._run(torch.from_numpy(np.ascontiguousarray(a)).cuda())
+        bits, its, post = self._run(torch.from_numpy(np.ascontiguousarray(a)).cuda(), None, return_llr)
+        if post is not None:
+            post = post.cpu().numpy()
         b = bits.cpu().numpy().astype(np.int64)
-        return (b, its.cpu().numpy().astype(np.int64)) if return_iterations else b
+        if out is not None:
+            out[...] = b
+            b = out
+        return pick(b, its.cpu().numpy().astype(np.int64), post)
 
 
 class BPDecoder(_LdpcBase):
@@ -124,6 +173,9 @@ class LayeredMSDecoder(_LdpcBase):
     share no column within a layer (default: layer_schedule(H));
     `[[c] for c in range(m)]` is the classic serial schedule."""
 
+    _soft_output = True
+    _host_out = True
+
     def __init__(self, H: np.ndarray, max_iter: int = 50, normalization: float = 1.0, early_stop: bool = True,
                  layers=None):
         self._algo = _native.PL_LDPC_LMS
@@ -142,57 +194,6 @@ class LayeredMSDecoder(_LdpcBase):
         # as MSDecoder: np.min over the other inputs of a degree-1 check is an empty reduction
         if self.max_iter > 0 and np.any(self.check_degrees == 1):
             raise ValueError("zero-size array to reduction operation minimum which has no identity")
-
-    def _run_soft(self, llr, out=None):
-        """Device batch: llr fp64 [B, >=n] -> (bits uint8 [B, n], iters int32 [B], posterior fp64 [B, n])."""
-        self._check_runnable()
-        B = llr.shape[0]
-        if out is None:
-            out = torch.empty((B, self.n), dtype=torch.uint8, device=llr.device)
-        iters = torch.empty((B,), dtype=torch.int32, device=llr.device)
-        post = torch.empty((B, self.n), dtype=torch.float64, device=llr.device)
-        if B > 0:
-            self.plan.decode_soft(llr, out, iters, post)
-        return out, iters, post
-
-    def decode_batch(self, llr, out: Optional[torch.Tensor] = None, return_iterations: bool = False,
-                     return_llr: bool = False):
-        """Bits [B, n]; with return_iterations / return_llr also the iteration
-        counts and the posterior LLRs, in the order bits, iterations, posterior.
-        A CUDA tensor in gives CUDA tensors out (no host copy; `out`: a uint8
-        [B, n] device tensor for the bits); NumPy in gives int64 / float64 NumPy
-        out (`out`: an int64 [B, n] array for the bits)."""
-
-        def pick(bits, its, post):
-            r = (bits,) + ((its,) if return_iterations else ()) + ((post,) if return_llr else ())
-            return r if len(r) > 1 else bits
-
-        if isinstance(llr, torch.Tensor) and llr.is_cuda:
-            assert llr.dim() == 2 and llr.shape[1] == self.n, "LLR length must be %d" % self.n
-            if llr.dtype != torch.float64 or llr.stride(1) != 1:
-                llr = llr.to(torch.float64).contiguous()
-            if return_llr:
-                return pick(*self._run_soft(llr, out))
-            bits, its = self._run(llr, out)
-            return pick(bits, its, None)
-        a = np.asarray(llr.cpu().numpy() if isinstance(llr, torch.Tensor) else llr, dtype=np.float64)
-        assert a.ndim == 2 and a.shape[1] == self.n, "LLR length must be %d" % self.n
-        if a.shape[0] == 0:
-            self._check_runnable()
-            bits = np.zeros((0, self.n), dtype=np.int64) if out is None else out
-            return pick(bits, np.zeros(0, dtype=np.int64), np.zeros((0, self.n), dtype=np.float64))
-        _native.require_gpu()
-        dev = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-        if return_llr:
-            bits, its, post = self._run_soft(dev)
-            post = post.cpu().numpy()
-        else:
-            (bits, its), post = self._run(dev), None
-        b = bits.cpu().numpy().astype(np.int64)
-        if out is not None:
-            out[...] = b
-            b = out
-        return pick(b, its.cpu().numpy().astype(np.int64), post)
 
     def decode(self, llr: np.ndarray, return_iterations: bool = False):
         assert len(llr) == self.n, f"LLR length must be {self.n}"
@@ -274,68 +275,25 @@ class QCLayeredMSDecoder(LayeredMSDecoder):
                                               _native.PL_LDPC_QC_F32 if self.dtype == np.float32 else 0)
         return self._plan
 
-    def _run_soft(self, llr, out=None):
+    # The dtype policy: what a float32 decoder changes about decode_batch.
+    @property
+    def _elem(self):
+        return self.dtype
+
+    def _device_llr(self, llr):
+        """float32 decoder: fp32 and fp64 tensors are read as they are (unit inner
+        stride, any row pitch); any other dtype is converted with .to(torch.float32)."""
         if self.dtype != np.float32:
-            return super()._run_soft(llr, out)
-        # llr fp32 or fp64 [B, >=n]; the posteriors are float32 (the state's type)
-        self._check_runnable()
-        B = llr.shape[0]
-        if out is None:
-            out = torch.empty((B, self.n), dtype=torch.uint8, device=llr.device)
-        iters = torch.empty((B,), dtype=torch.int32, device=llr.device)
-        post = torch.empty((B, self.n), dtype=torch.float32, device=llr.device)
-        if B > 0 and llr.dtype == torch.float32:
-            self.plan.decode_soft(llr, out, iters, post)
-        elif B > 0:  # fp64 in: the fp64-I/O instance widens the float32 posteriors, which rounds back exactly
-            wide = torch.empty((B, self.n), dtype=torch.float64, device=llr.device)
-            self.plan.decode_soft(llr, out, iters, wide)
-            post.copy_(wide)
-        return out, iters, post
+            return super()._device_llr(llr)
+        if llr.dtype not in (torch.float32, torch.float64):
+            llr = llr.to(torch.float32)
+        return llr if llr.stride(1) == 1 else llr.contiguous()
 
-    def decode_batch(self, llr, out: Optional[torch.Tensor] = None, return_iterations: bool = False,
-                     return_llr: bool = False):
-        """As LayeredMSDecoder.decode_batch.  On a float32 decoder a CUDA float32
-        or float64 tensor (unit inner stride, any row pitch) is decoded in place,
-        any other CUDA float dtype is converted with .to(torch.float32), NumPy
-        input with astype(np.float32), and return_llr gives float32 posteriors
-        (from fp64 LLRs through an fp64 buffer and one narrowing copy: the class
-        docstring)."""
+    def _host_llr(self, llr):
         if self.dtype != np.float32:
-            return super().decode_batch(llr, out, return_iterations, return_llr)
-
-        def pick(bits, its, post):
-            r = (bits,) + ((its,) if return_iterations else ()) + ((post,) if return_llr else ())
-            return r if len(r) > 1 else bits
-
-        if isinstance(llr, torch.Tensor) and llr.is_cuda:
-            assert llr.dim() == 2 and llr.shape[1] == self.n, "LLR length must be %d" % self.n
-            if llr.dtype not in (torch.float32, torch.float64):
-                llr = llr.to(torch.float32)
-            if llr.stride(1) != 1:
-                llr = llr.contiguous()
-            if return_llr:
-                return pick(*self._run_soft(llr, out))
-            bits, its = self._run(llr, out)
-            return pick(bits, its, None)
+            return super()._host_llr(llr)
         with np.errstate(all="ignore"):  # beyond FLT_MAX: +-inf, by definition
-            a = np.asarray(llr.cpu().numpy() if isinstance(llr, torch.Tensor) else llr).astype(np.float32)
-        assert a.ndim == 2 and a.shape[1] == self.n, "LLR length must be %d" % self.n
-        if a.shape[0] == 0:
-            self._check_runnable()
-            bits = np.zeros((0, self.n), dtype=np.int64) if out is None else out
-            return pick(bits, np.zeros(0, dtype=np.int64), np.zeros((0, self.n), dtype=np.float32))
-        _native.require_gpu()
-        dev = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-        if return_llr:
-            bits, its, post = self._run_soft(dev)
-            post = post.cpu().numpy()
-        else:
-            (bits, its), post = self._run(dev), None
-        b = bits.cpu().numpy().astype(np.int64)
-        if out is not None:
-            out[...] = b
-            b = out
-        return pick(b, its.cpu().numpy().astype(np.int64), post)
+            return np.asarray(llr).astype(np.float32)
 
     def __repr__(self) -> str:
         return (f"QCLayeredMSDecoder(n={self.n}, m={self.m}, Z={self.Z}, max_iter={self.max_iter}, "

@@ -74,6 +74,9 @@ int main() {
     int64_t ws = 0;
     EXPECT(pl_decode(nullptr, llr, 1, 8, bits, nullptr, nullptr) == PL_EINVAL);
     EXPECT(pl_decode_ws(nullptr, llr, 1, 8, bits, nullptr, nullptr, 0, nullptr) == PL_EINVAL);
+    float llr32[8] = {0};
+    EXPECT(pl_ldpc_decode_soft(nullptr, llr, 1, 8, bits, nullptr, llr, 8, nullptr) == PL_EINVAL);
+    EXPECT(pl_ldpc_decode_f32(nullptr, llr32, 1, 8, bits, nullptr, nullptr, 0, nullptr, 0, nullptr) == PL_EINVAL);
     EXPECT(pl_plan_workspace_bytes(nullptr, 1, &ws) == PL_EINVAL);
     EXPECT(pl_plan_reserve(nullptr, 1, nullptr) == PL_EINVAL);
     EXPECT(pl_plan_release(nullptr, nullptr) == PL_EINVAL);
@@ -95,6 +98,17 @@ int main() {
     EXPECT(pl_gf2_encode(nullptr, 4, 8, bits, 4, 1, bits, 8, nullptr) == PL_EINVAL);
     EXPECT(pl_count_errors(bits, 8, bits, 8, 8, 1, nullptr, nullptr) == PL_EINVAL);
     EXPECT(pl_polar_encode(nullptr, bits, 1, bits, nullptr) == PL_EINVAL);
+    // quasi-cyclic encoder: a null encoder, and base matrices refused before any device call
+    pl_qc_encoder* enc = reinterpret_cast<pl_qc_encoder*>(0x1);
+    EXPECT(pl_ldpc_qc_encode(nullptr, bits, 8, 1, bits, 8, nullptr) == PL_EINVAL);
+    std::vector<int32_t> base = {0, 1, 0, -1, 2, 0, 1, 0};  // [2, 4], Z = 3
+    EXPECT(pl_ldpc_qc_encoder_create(2, 4, 3, base.data(), nullptr) == PL_EINVAL);
+    base[1] = 3;  // a shift of Z
+    EXPECT(pl_ldpc_qc_encoder_create(2, 4, 3, base.data(), &enc) == PL_EINVAL && enc == nullptr &&
+           std::strstr(pl_last_error(), "outside -1 .. Z-1"));
+    EXPECT(pl_ldpc_qc_encoder_create(2, 2, 3, base.data(), &enc) == PL_EINVAL && enc == nullptr);  // no message column
+    EXPECT(pl_ldpc_qc_encoder_create(2, 4, 3, nullptr, &enc) == PL_EINVAL && enc == nullptr);
+    EXPECT(pl_ldpc_qc_encoder_destroy(nullptr) == PL_OK);
     if (failures) {
         std::fprintf(stderr, "%d failure(s)\n", failures);
         return 1;
