@@ -80,3 +80,44 @@ def test_ldpc_decode_replayed_from_graph(gpu):
         torch.cuda.synchronize()
         assert np.array_equal(out.cpu().numpy(), bits_exp[part])
         assert np.array_equal(its.cpu().numpy(), its_exp[part])
+
+
+@pytest.mark.parametrize("state_home", ["lds", "workspace"])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_qc_ldpc_decode_replayed_from_graph(gpu, monkeypatch, dtype, state_home):
+    """The quasi-cyclic layered decoder on a caller-owned workspace, captured once and replayed on two
+    inputs: pl_decode_ws (fp64 LLRs) and pl_ldpc_decode_f32 with workspace_dev set (fp32 LLRs on a
+    PL_LDPC_QC_F32 plan), state in LDS and in the workspace, against the base-matrix restatement."""
+    import polarcode_and_ldpc_amd.ldpc as L
+    from qc_layered_ref import qc_layered_ms_ref
+    if state_home == "workspace":
+        monkeypatch.setenv("PL_LMS_GLOBAL", "1")
+    Z, h = 27, 19  # 19 frames: two workgroups of 8 and a ragged third
+    base = L.qc_random_base(4, 8, Z, 3, seed=135)
+    rng = np.random.RandomState(27)
+    sigma = np.sqrt(1.0 / (2.0 * 10.0 ** (-1.0 / 10.0)))
+    llr_all = (2.0 * (1.0 + sigma * rng.randn(2 * h, 8 * Z)) / sigma ** 2).astype(dtype)
+    want = qc_layered_ms_ref(base, Z, llr_all, 20, 0.75, True, dtype=dtype)
+    for part in (slice(0, h), slice(h, 2 * h)):
+        assert want[1][part].min() < 20 and want[1][part].max() == 20
+    assert not np.array_equal(want[1][:h], want[1][h:])
+    plan = L.QCLayeredMSDecoder(base, Z, max_iter=20, normalization=0.75, dtype=dtype).plan
+    f32 = dtype == np.float32
+    assert plan.info.reserved == {("lds", False): 11, ("workspace", False): 12, ("lds", True): 13,
+                                  ("workspace", True): 14}[(state_home, f32)]
+    assert (plan.workspace_bytes(h) > 0) == (state_home == "workspace")
+    llr = torch.from_numpy(np.ascontiguousarray(llr_all[:h])).cuda()
+    assert llr.dtype == (torch.float32 if f32 else torch.float64)
+    out = torch.empty((h, 8 * Z), dtype=torch.uint8, device="cuda")
+    its = torch.empty((h,), dtype=torch.int32, device="cuda")
+    ws = torch.empty(max(1, plan.workspace_bytes(h)), dtype=torch.uint8, device="cuda")
+    g = _capture(lambda: plan.decode(llr, out, its, ws=ws))
+    assert plan.workspace_stats() == (0, 0)  # the caller's workspace only
+    for part in (slice(0, h), slice(h, 2 * h)):
+        llr.copy_(torch.from_numpy(np.ascontiguousarray(llr_all[part])))
+        out.fill_(7)
+        its.fill_(-1)
+        g.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(out.cpu().numpy(), want[0][part])
+        assert np.array_equal(its.cpu().numpy(), want[1][part])
