@@ -522,6 +522,73 @@ int pl_debug_ldpc_qc_encoder_probe(int32_t mb, int32_t nb, int32_t z, const int3
  * pl_debug_set_plan_device for an encoder. */
 int pl_debug_set_qc_encoder_device(pl_qc_encoder* enc, int32_t device);
 
+/* ---- Rate matching for quasi-cyclic LDPC codes: puncture, shorten, repeat ---------
+ * Which bits of a codeword of the code (mb, nb, z) are transmitted, and how their
+ * LLRs come back to codeword positions.  This comment is the definition; the
+ * kernels (ldpc_qc_ratematch.hip), ldpc.QCRateMatcher and the harness cite it.
+ * Parameters and conditions (n = nb z, kb = nb - mb >= 1, k = kb z):
+ *   punctured  leading block columns never transmitted; P = punctured z,
+ *              0 <= punctured < kb
+ *   fillers    F: the last F message bits (codeword positions k-F .. k-1) are
+ *              known zeros and never transmitted; 0 <= F <= k - P
+ *   ncb        the circular buffer is codeword positions P .. P+ncb-1;
+ *              k - P <= ncb <= n - P; a negative ncb asks for the default n - P
+ *   start      where reading begins in the buffer, 0 <= start < ncb; any value,
+ *              not only multiples of z
+ *   E >= 1     transmitted bits per frame
+ *   M = ncb - F >= 1   the buffer without its fillers
+ * Selection: t = 0, j = 0; while t < E: b = (start + j) mod ncb; if buffer
+ *   position b is no filler (not k-P-F <= b < k-P): e[t] = c[P + b], t += 1;
+ *   j += 1.
+ * Closed form (what the kernels compute; there is no table):
+ *   compact index of a non-filler buffer position b: c(b) = b for b < k-P-F,
+ *   else b - F; c0 = c(start) if start is no filler, else (k-P-F) mod M;
+ *   transmitted bit t is compact index (c0 + t) mod M; the position of compact
+ *   index c receives t = r, r+M, r+2M, ... < E with r = (c - c0) mod M.
+ *   hi: the highest transmitted codeword position; max_reps = ceil(E / M).
+ * Recovery of out[b][0:n_out], element type T (fp64 or fp32), from llr[b][0:E]
+ * (fp64 or fp32); hi < n_out <= n:
+ *   a transmitted position gets its terms, each converted to T, summed left to
+ *   right in ascending t starting from the first term (a single term is a copy:
+ *   -0.0 stays -0.0); a filler gets +filler_llr (the sign that decodes to bit 0:
+ *   pl_awgn_llr maps 0 -> +1), converted to T; every other position +0.0.
+ *   PL_RM_ACCUMULATE (soft combining of retransmissions): out holds an earlier
+ *   recovery; transmitted positions become out[pos] + s, s the sum above, and
+ *   every other position keeps its value.
+ * pl_ldpc_rate_match_check fills the derived fields from the parameters;
+ * PL_EINVAL naming the first condition violated, in the order above.  It makes no
+ * device call.  The two kernels take the struct by value: there is no device
+ * object.  pl_ldpc_rate_match and pl_ldpc_rate_recover derive the fields again
+ * themselves, so a caller's derived fields are never trusted. */
+typedef struct {
+    int32_t mb, nb, z;                           /* the code                                   */
+    int32_t punctured, fillers, ncb, start, E;   /* ncb < 0 on input: n - P                    */
+    int32_t n, k, P, M, c0, hi, max_reps;        /* derived by pl_ldpc_rate_match_check        */
+} pl_rate_match;
+int pl_ldpc_rate_match_check(pl_rate_match* rm);
+/* The same from plain arguments (the planner's window for tests, as pl_debug_ldpc_qc_encoder_probe). */
+int pl_debug_rate_match_probe(int32_t mb, int32_t nb, int32_t z, int32_t punctured, int32_t fillers, int32_t ncb,
+                              int32_t start, int32_t E, pl_rate_match* out);
+/* e[b][t] = cw[b][position of t], t < E: cw_dev uint8 [batch][ld_cw], ld_cw >= n,
+ * bytes copied as they are; e_dev uint8 [batch][ld_e], ld_e >= E, bytes beyond E
+ * are left alone.  Asynchronous on `stream`; batch == 0 launches nothing.
+ * PL_EINVAL for what pl_ldpc_rate_match_check refuses, a NULL pointer, batch < 0
+ * and a short pitch; every check runs before the first device call. */
+int pl_ldpc_rate_match(const pl_rate_match* rm, const uint8_t* cw_dev, int64_t ld_cw, int64_t batch, uint8_t* e_dev,
+                       int64_t ld_e, void* stream);
+#define PL_RM_LLR_F32 1    /* llr_dev is float (else double)                           */
+#define PL_RM_OUT_F32 2    /* out_dev is float (else double)                           */
+#define PL_RM_ACCUMULATE 4 /* add to the recovery out_dev already holds                */
+/* Recovery as defined above: llr_dev [batch][ld_llr], ld_llr >= E; out_dev
+ * [batch][ld_out], ld_out >= n_out, elements beyond n_out are left alone; pitches
+ * in elements.  Asynchronous on `stream`; batch == 0 launches nothing.  PL_EINVAL
+ * as pl_ldpc_rate_match, and for n_out <= hi, n_out > n, unknown flag bits and a
+ * pointer that is not aligned to its element type.
+ * Both kernels cut each row at the 16-byte boundaries of its output addresses and
+ * store whole pieces 16 bytes wide, whatever the pointer and the pitch. */
+int pl_ldpc_rate_recover(const pl_rate_match* rm, const void* llr_dev, int64_t ld_llr, int64_t batch, void* out_dev,
+                         int64_t ld_out, int32_t n_out, double filler_llr, int32_t flags, void* stream);
+
 /* Error counting (benchmarks/ber_simulation.py:180-189):
  * counts_dev[0] += bit errors, [1] += frame errors, [2] += frames, over the
  * first `width` entries of each row.  counts_dev int64[3], device. */

@@ -30,8 +30,10 @@ EXPORTS = (
     "pl_debug_ldpc_plan_probe", "pl_debug_ldpc_layered_plan_probe", "pl_ldpc_qc_plan_create",
     "pl_debug_ldpc_qc_plan_probe", "pl_ldpc_decode_f32", "pl_debug_ldpc_qc_plan_probe_flags",
     "pl_ldpc_qc_encoder_create", "pl_ldpc_qc_encode", "pl_ldpc_qc_encoder_destroy", "pl_debug_ldpc_qc_encoder_probe",
-    "pl_debug_set_qc_encoder_device",
+    "pl_debug_set_qc_encoder_device", "pl_ldpc_rate_match_check", "pl_debug_rate_match_probe", "pl_ldpc_rate_match",
+    "pl_ldpc_rate_recover",
 )
+PL_RM_LLR_F32, PL_RM_OUT_F32, PL_RM_ACCUMULATE = 1, 2, 4  # pl_ldpc_rate_recover flags
 
 
 class PlanInfo(ctypes.Structure):
@@ -71,6 +73,12 @@ class QcEncoderProbe(ctypes.Structure):
                [("table_len", ctypes.c_int64), ("digest", ctypes.c_uint64)]
 
 
+class RateMatch(ctypes.Structure):
+    """pl_rate_match: the parameters of a rate matching and the fields pl_ldpc_rate_match_check derives."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("mb", "nb", "z", "punctured", "fillers", "ncb", "start", "E",
+                                              "n", "k", "P", "M", "c0", "hi", "max_reps")]
+
+
 def _load(path=LIB_PATH):
     if not os.path.exists(path):
         raise ImportError(
@@ -95,6 +103,10 @@ def _load(path=LIB_PATH):
     L.pl_ldpc_qc_encoder_destroy.argtypes = [P]
     L.pl_debug_ldpc_qc_encoder_probe.argtypes = [I32, I32, I32, P, ctypes.POINTER(QcEncoderProbe)]
     L.pl_debug_set_qc_encoder_device.argtypes = [P, I32]
+    L.pl_ldpc_rate_match_check.argtypes = [ctypes.POINTER(RateMatch)]
+    L.pl_debug_rate_match_probe.argtypes = [I32] * 8 + [ctypes.POINTER(RateMatch)]
+    L.pl_ldpc_rate_match.argtypes = [ctypes.POINTER(RateMatch), P, I64, I64, P, I64, P]
+    L.pl_ldpc_rate_recover.argtypes = [ctypes.POINTER(RateMatch), P, I64, I64, P, I64, I32, D, I32, P]
     L.pl_ldpc_decode_soft.argtypes = [P, P, I64, I64, P, P, P, I64, P]
     L.pl_ldpc_decode_f32.argtypes = [P, P, I64, I64, P, P, P, I64, P, I64, P]
     L.pl_decode.argtypes = [P, P, I64, I64, P, P, P]
@@ -413,6 +425,30 @@ def qc_encoder(base: np.ndarray, Z: int) -> QcEncoder:
     check(lib.pl_ldpc_qc_encoder_create(sh.shape[0], sh.shape[1], int(Z), sh.ctypes.data_as(ctypes.c_void_p),
                                         ctypes.byref(h)), "pl_ldpc_qc_encoder_create")
     return QcEncoder(h, (sh.shape[1] - sh.shape[0]) * int(Z), sh.shape[1] * int(Z))
+
+
+def rate_match_probe(mb: int, nb: int, Z: int, punctured: int, fillers: int, ncb: int, start: int, E: int) -> RateMatch:
+    """pl_debug_rate_match_probe: the checked parameters with the derived fields (no device call); ncb < 0:
+    the default n - P.  AssertionError with the first violated condition."""
+    rm = RateMatch()
+    check(lib.pl_debug_rate_match_probe(int(mb), int(nb), int(Z), int(punctured), int(fillers), int(ncb), int(start),
+                                        int(E), ctypes.byref(rm)), "pl_debug_rate_match_probe")
+    return rm
+
+
+def rate_match(rm: RateMatch, cw: "torch.Tensor", e: "torch.Tensor", stream=None):
+    """pl_ldpc_rate_match: cw uint8 [B, >= n], e uint8 [B, >= E]: device tensors, unit inner stride, any row pitch."""
+    check(lib.pl_ldpc_rate_match(ctypes.byref(rm), cw.data_ptr(), _ld(cw), cw.shape[0], e.data_ptr(), _ld(e),
+                                 _stream(stream)), "pl_ldpc_rate_match")
+
+
+def rate_recover(rm: RateMatch, llr: "torch.Tensor", out: "torch.Tensor", n_out: int, filler_llr: float,
+                 accumulate: bool = False, stream=None):
+    """pl_ldpc_rate_recover: llr [B, >= E], out [B, >= n_out], each float64 or float32 on the device."""
+    flags = (PL_RM_LLR_F32 if llr.dtype == torch.float32 else 0) | (PL_RM_OUT_F32 if out.dtype == torch.float32 else 0) \
+        | (PL_RM_ACCUMULATE if accumulate else 0)
+    check(lib.pl_ldpc_rate_recover(ctypes.byref(rm), llr.data_ptr(), _ld(llr), llr.shape[0], out.data_ptr(), _ld(out),
+                                   int(n_out), float(filler_llr), flags, _stream(stream)), "pl_ldpc_rate_recover")
 
 
 def random_bits(seed: int, frame_offset: int, bits: "torch.Tensor", stream=None):

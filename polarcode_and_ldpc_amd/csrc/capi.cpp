@@ -1156,6 +1156,62 @@ extern "C" int pl_debug_set_qc_encoder_device(pl_qc_encoder* enc, int32_t device
 #endif
 }
 
+// ---- rate matching of quasi-cyclic codes (ldpc_qc_ratematch.hip) ----
+extern "C" int pl_ldpc_rate_match_check(pl_rate_match* rm) {
+    const pl::PlanStatus st = pl::rate_match_check(rm);
+    return st.code ? fail(st.code, st.msg) : PL_OK;
+}
+
+extern "C" int pl_debug_rate_match_probe(int32_t mb, int32_t nb, int32_t z, int32_t punctured, int32_t fillers,
+                                         int32_t ncb, int32_t start, int32_t E, pl_rate_match* out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    pl_rate_match rm{};
+    rm.mb = mb; rm.nb = nb; rm.z = z;
+    rm.punctured = punctured; rm.fillers = fillers; rm.ncb = ncb; rm.start = start; rm.E = E;
+    if (int rc = pl_ldpc_rate_match_check(&rm)) return rc;
+    *out = rm;
+    return PL_OK;
+}
+
+// the caller's parameters, checked and derived afresh; every check comes before the first device call
+static int rate_match_args(const pl_rate_match* in, pl_rate_match* rm, const void* a, const void* b, int64_t batch) {
+    if (!in) return fail(PL_EINVAL, "rate match is NULL");
+    *rm = *in;
+    if (int rc = pl_ldpc_rate_match_check(rm)) return rc;
+    if (!a || !b) return fail(PL_EINVAL, "device pointers must not be NULL");
+    if (batch < 0) return fail(PL_EINVAL, "batch must be >= 0");
+    return PL_OK;
+}
+
+extern "C" int pl_ldpc_rate_match(const pl_rate_match* in, const uint8_t* cw, int64_t ld_cw, int64_t batch, uint8_t* e,
+                                  int64_t ld_e, void* stream) {
+    pl_rate_match rm;
+    if (int rc = rate_match_args(in, &rm, cw, e, batch)) return rc;
+    if (ld_cw < rm.n) return fail(PL_EINVAL, "ld_cw < n = " + std::to_string(rm.n));
+    if (ld_e < rm.E) return fail(PL_EINVAL, "ld_e < E = " + std::to_string(rm.E));
+    const hipError_t err = pl::rate_match_launch(rm, cw, ld_cw, batch, e, ld_e, (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "rate match launch");
+}
+
+extern "C" int pl_ldpc_rate_recover(const pl_rate_match* in, const void* llr, int64_t ld_llr, int64_t batch, void* out,
+                                    int64_t ld_out, int32_t n_out, double filler_llr, int32_t flags, void* stream) {
+    pl_rate_match rm;
+    if (int rc = rate_match_args(in, &rm, llr, out, batch)) return rc;
+    if (flags & ~(PL_RM_LLR_F32 | PL_RM_OUT_F32 | PL_RM_ACCUMULATE)) return fail(PL_EINVAL, "unknown flag bits");
+    if (n_out <= rm.hi)
+        return fail(PL_EINVAL, "n_out = " + std::to_string(n_out) + " does not reach the highest transmitted position " +
+                                   std::to_string(rm.hi));
+    if (n_out > rm.n) return fail(PL_EINVAL, "n_out = " + std::to_string(n_out) + " > n = " + std::to_string(rm.n));
+    if (((uintptr_t)llr & ((flags & PL_RM_LLR_F32) ? 3 : 7)) || ((uintptr_t)out & ((flags & PL_RM_OUT_F32) ? 3 : 7)))
+        return fail(PL_EINVAL, "llr_dev and out_dev must be aligned to their element type");
+    if (ld_llr < rm.E) return fail(PL_EINVAL, "ld_llr < E = " + std::to_string(rm.E));
+    if (ld_out < n_out) return fail(PL_EINVAL, "ld_out < n_out = " + std::to_string(n_out));
+    const hipError_t err = pl::rate_recover_launch(rm, llr, ld_llr, flags & PL_RM_LLR_F32, batch, out, ld_out,
+                                                   flags & PL_RM_OUT_F32, n_out, filler_llr,
+                                                   flags & PL_RM_ACCUMULATE, (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "rate recover launch");
+}
+
 extern "C" int pl_count_errors(const uint8_t* ref, int64_t ldr, const uint8_t* dec, int64_t ldd, int32_t width,
                                int64_t batch, int64_t* counts, void* stream) {
     if (batch < 0 || width < 0 || !counts || (batch > 0 && (!ref || !dec))) return fail(PL_EINVAL, "bad argument");

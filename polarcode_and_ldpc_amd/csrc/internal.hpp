@@ -150,4 +150,13 @@ hipError_t qc_encode_prepare(const QcEncGeom& g);
 hipError_t qc_encode_launch(const QcEncGeom& g, const int32_t* tab, const uint8_t* msg, int64_t ldm, int64_t batch,
                             uint8_t* cw, int64_t ldc, hipStream_t s);
 
+// ---- rate matching of quasi-cyclic codes (ldpc_qc_ratematch.hip); pl_rate_match: include/polarldpc.h ----
+// rm: checked (rate_match_check).  cw uint8 [batch][ldc], e uint8 [batch][lde]; llr [batch][ldl] float or
+// double, out [batch][ldo] float or double, pitches in elements.  Both chunk their launches themselves.
+hipError_t rate_match_launch(const pl_rate_match& rm, const uint8_t* cw, int64_t ldc, int64_t batch, uint8_t* e,
+                             int64_t lde, hipStream_t s);
+hipError_t rate_recover_launch(const pl_rate_match& rm, const void* llr, int64_t ldl, bool llr_f32, int64_t batch,
+                               void* out, int64_t ldo, bool out_f32, int n_out, double filler, bool acc,
+                               hipStream_t s);
+
 }  // namespace pl

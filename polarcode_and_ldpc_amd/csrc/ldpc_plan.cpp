@@ -640,4 +640,37 @@ PlanStatus qc_encoder_plan_build(int mb, int nb, int z, const int32_t* shift, Qc
     return {};
 }
 
+// ---- rate matching (include/polarldpc.h, pl_rate_match) ----
+PlanStatus rate_match_check(pl_rate_match* rm) {
+    if (!rm) return refuse(PL_EINVAL, "rate match is NULL");
+    const auto S = [](int64_t v) { return std::to_string(v); };
+    if (rm->mb < 1 || rm->nb < 1 || rm->z < 1) return refuse(PL_EINVAL, "mb, nb and Z must be >= 1");
+    const int64_t z = rm->z, kb = (int64_t)rm->nb - rm->mb;
+    if (kb < 1) return refuse(PL_EINVAL, "kb = nb - mb must be >= 1 (no message block column)");
+    const int64_t n = (int64_t)rm->nb * z, k = kb * z;
+    if (n > INT32_MAX) return refuse(PL_EINVAL, "nb Z must fit 32 bits");
+    if (rm->punctured < 0 || rm->punctured >= kb)
+        return refuse(PL_EINVAL, "punctured = " + S(rm->punctured) + " outside 0 .. kb-1 = " + S(kb - 1));
+    const int64_t P = (int64_t)rm->punctured * z, F = rm->fillers;
+    if (F < 0 || F > k - P) return refuse(PL_EINVAL, "fillers = " + S(F) + " outside 0 .. k - P = " + S(k - P));
+    const int64_t ncb = rm->ncb < 0 ? n - P : rm->ncb;
+    if (ncb < k - P || ncb > n - P)
+        return refuse(PL_EINVAL, "ncb = " + S(ncb) + " outside k - P = " + S(k - P) + " .. n - P = " + S(n - P));
+    if (rm->start < 0 || rm->start >= ncb)
+        return refuse(PL_EINVAL, "start = " + S(rm->start) + " outside 0 .. ncb-1 = " + S(ncb - 1));
+    if (rm->E < 1) return refuse(PL_EINVAL, "E = " + S(rm->E) + " must be >= 1");
+    const int64_t M = ncb - F;
+    if (M < 1) return refuse(PL_EINVAL, "M = ncb - fillers = " + S(M) + " must be >= 1 (nothing to transmit)");
+    const int64_t lo = k - P - F;  // buffer positions lo .. lo+F-1 are the fillers
+    const int64_t start = rm->start, E = rm->E;
+    const int64_t c0 = start < lo ? start : start >= lo + F ? start - F : lo % M;
+    // compact indices c0 .. c0+E-1 mod M: the largest one, then its codeword position
+    const int64_t cmax = c0 + E - 1 < M ? c0 + E - 1 : M - 1;
+    rm->ncb = (int32_t)ncb;
+    rm->n = (int32_t)n; rm->k = (int32_t)k; rm->P = (int32_t)P; rm->M = (int32_t)M; rm->c0 = (int32_t)c0;
+    rm->hi = (int32_t)(P + (cmax < lo ? cmax : cmax + F));
+    rm->max_reps = (int32_t)((E + M - 1) / M);
+    return {};
+}
+
 }  // namespace pl

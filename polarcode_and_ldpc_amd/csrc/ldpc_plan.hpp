@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/polarldpc.h"  // pl_rate_match
+
 namespace pl {
 
 // ---- kernel arguments (field order and types are the kernels' ABI) ----
@@ -262,6 +264,13 @@ struct QcEncHostPlan {
 // PL_EUNSUPPORTED: z > kQcMaxZ, a parity part outside the structure (the message names the first rule
 // violated), a workgroup's LDS above kQcEncLdsMax.
 PlanStatus qc_encoder_plan_build(int mb, int nb, int z, const int32_t* shift, QcEncHostPlan* out);
+
+// ---- rate matching of quasi-cyclic codes (ldpc_qc_ratematch.hip) ----
+// The definition: include/polarldpc.h, pl_rate_match.  The struct is plain data and the kernels' argument
+// (passed by value): no table, no device object.  rate_match_check validates the parameters in the
+// header's order (PL_EINVAL, the message names the first condition violated) and fills n, k, P, M, c0,
+// hi and max_reps; a negative ncb becomes n - P.
+PlanStatus rate_match_check(pl_rate_match* rm);
 
 // 64-bit FNV-1a over a table vector's bytes (the pl_debug_*_plan_probe digests)
 uint64_t plan_tables_digest(const std::vector<int32_t>& tables);

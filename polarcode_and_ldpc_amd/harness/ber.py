@@ -99,17 +99,37 @@ def simulate_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: in
 
 def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: int, base, Z: int,
                      max_iter: int = 20, normalization: float = 0.75, dtype=np.float64, batch: int = 65536,
-                     seed: int = 0, group=None, random_codewords: bool = False, log_path=None):
+                     seed: int = 0, group=None, random_codewords: bool = False, log_path=None, rate_match=None):
     """simulate_ldpc for the quasi-cyclic code (base, Z): QCLayeredMSDecoder (layered
     normalised min-sum, early stop, state in `dtype`) on frames of the all-zero
     codeword or, random_codewords, of random messages encoded on the device from
     the base matrix (QCLDPCEncoder: base must have its structure, e.g. from
     qc_encodable_base).  H is never expanded.  -> (ber, fer, points), errors over
-    the k = (nb - mb) Z message positions."""
+    the k = (nb - mb) Z message positions.
+
+    rate_match: None, or QCRateMatcher's arguments behind (base, Z) -- a dict, or
+    the sequence (E, punctured, fillers[, ncb[, start]]): E bits of each frame are
+    transmitted (ldpc_round_fn's rate_matcher), the decoder works on the
+    matcher's decoder_base(), errors over the k - fillers message positions."""
     import torch
     from ..ldpc.decoder import QCLayeredMSDecoder
     from ..ldpc.encoder import QCLDPCEncoder
     base = np.asarray(base, dtype=np.int64)
+    if rate_match is not None:
+        from ..ldpc.ratematch import QCRateMatcher
+        rm = QCRateMatcher(base, Z, **rate_match) if isinstance(rate_match, dict) else QCRateMatcher(base, Z, *rate_match)
+        dec = QCLayeredMSDecoder(rm.decoder_base(), Z, max_iter=max_iter, normalization=normalization,
+                                 early_stop=True, dtype=dtype)
+        k = rm.k - rm.fillers
+        enc = QCLDPCEncoder(base, Z) if random_codewords else None
+        mc = MonteCarlo(ldpc_round_fn(dec, seed=seed, encoder=enc, rate_matcher=rm), info_bits=k, batch=batch,
+                        group=group, device=torch.device("cuda", torch.cuda.current_device()))
+        log = _log(log_path, mc, code="qcldpc", n=rm.n, k=k, Z=int(Z), max_iter=max_iter, norm=float(normalization),
+                   dtype=np.dtype(dec.dtype).name, random=random_codewords, frames=num_frames, max_errors=max_errors,
+                   seed=seed, base=_digest(base + 1), rm=[rm.E, rm.punctured, rm.fillers, rm.ncb, rm.start],
+                   filler_llr=rm.filler_llr, n_dec=rm.n_dec)
+        pts = mc.run(snr_db_range, num_frames, max_errors, log=log)
+        return np.array([p.ber for p in pts]), np.array([p.fer for p in pts]), pts
     dec = QCLayeredMSDecoder(base, Z, max_iter=max_iter, normalization=normalization, early_stop=True, dtype=dtype)
     k = dec.n - dec.m
     enc = QCLDPCEncoder(base, Z) if random_codewords else None
@@ -179,6 +199,9 @@ def main(argv=None):
                     help="LDPC frames: all-zero codeword, or random messages encoded on the device")
     ap.add_argument("--qc", default="12,24,81,3,1",
                     help="--code qcldpc: mb,nb,Z,dv,seed[,core], the code qc_encodable_base(mb, nb, Z, dv, seed, core)")
+    ap.add_argument("--rm", default=None,
+                    help="--code qcldpc: E,punctured,fillers[,ncb[,start]], rate matching (ldpc.QCRateMatcher): E bits "
+                         "of each frame are transmitted")
     ap.add_argument("--dtype", choices=["float64", "float32"], default="float64",
                     help="--code qcldpc: the decoder's state and arithmetic")
     ap.add_argument("--norm", type=float, default=0.75, help="--code qcldpc: min-sum normalisation")
@@ -212,9 +235,16 @@ def main(argv=None):
         if len(q) not in (5, 6):
             ap.error("--qc takes mb,nb,Z,dv,seed[,core]")
         base = qc_encodable_base(*q[:5], core=q[5] if len(q) == 6 else None)
+        rm = None
+        if a.rm is not None:
+            rm = [int(x) for x in a.rm.split(",")]
+            if len(rm) not in (3, 4, 5):
+                ap.error("--rm takes E,punctured,fillers[,ncb[,start]]")
+        more = {} if rm is None else {"rate_match": rm}
         ber, fer, pts = simulate_qc_ldpc(snr, a.frames, a.max_errors, base, q[2], max_iter=a.max_iter,
                                          normalization=a.norm, dtype=np.dtype(a.dtype).type, batch=a.batch,
-                                         seed=a.seed, random_codewords=a.ldpc_codewords == "random", log_path=a.log)
+                                         seed=a.seed, random_codewords=a.ldpc_codewords == "random", log_path=a.log,
+                                         **more)
     else:
         ber, fer, pts = simulate_ldpc(snr, a.frames, a.max_errors,
                                       {"encoding": {"n": a.n, "k": a.k}, "decoding": {"max_iterations": a.max_iter}},

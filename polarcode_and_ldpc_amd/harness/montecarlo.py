@@ -248,7 +248,53 @@ def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None)
     return fn
 
 
-def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encoder=None):
+def _rate_matched_round_fn(decoder, seed, encoder, rm):
+    """ldpc_round_fn's rate-matched chain; see there."""
+    import torch
+    from .. import _native
+    from ..channel.awgn import AWGNChannel
+    n_dec, E, kf = rm.n_dec, rm.E, rm.k - rm.fillers
+    assert decoder.n == n_dec, "the decoder must be built on rate_matcher.decoder_base(): n = %d" % n_dec
+    assert kf >= 1, "every message bit is a filler: no error to count"
+    assert encoder is None or (encoder.n == rm.n and encoder.k == rm.k
+                               and np.array_equal(encoder.info_positions, np.arange(rm.k))), \
+        "the encoder must be the systematic encoder of the rate matcher's code"
+    ftype = torch.float32 if np.dtype(getattr(decoder, "dtype", np.float64)) == np.float32 else torch.float64
+    bufs = {}
+
+    def fn(snr_index, snr_db, offset, nframes):
+        if bufs.get("B", 0) < nframes:
+            bufs.update(B=nframes, rx=torch.empty((nframes, E), dtype=torch.float64, device="cuda"),
+                        llr=torch.empty((nframes, n_dec), dtype=ftype, device="cuda"),
+                        out=torch.empty((nframes, n_dec), dtype=torch.uint8, device="cuda"),
+                        its=torch.empty((nframes,), dtype=torch.int32, device="cuda"),
+                        zero=torch.zeros((nframes, kf), dtype=torch.uint8, device="cuda"),
+                        msg=torch.empty((nframes, rm.k), dtype=torch.uint8, device="cuda"),
+                        cw=torch.empty((nframes, rm.n), dtype=torch.uint8, device="cuda"),
+                        tx=torch.empty((nframes, E), dtype=torch.uint8, device="cuda"))
+        rx, llr, out, its, zero, msg, cw, tx = (bufs[x][:nframes] for x in ("rx", "llr", "out", "its", "zero", "msg",
+                                                                            "cw", "tx"))
+        s = _stream_seed(seed, snr_index)
+        counts = torch.zeros(3, dtype=torch.int64, device="cuda")
+        if encoder is None:
+            AWGNChannel(snr_db).llr_batch_device(None, E, nframes, seed=s, frame_offset=offset, out=rx)
+            ref = zero
+        else:
+            _native.random_bits(s, offset, msg)
+            msg[:, kf:] = 0  # the fillers are known zeros
+            encoder.encode_batch_device(msg, out=cw)
+            rm.select(cw, out=tx)
+            AWGNChannel(snr_db).llr_batch_device(tx, E, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=rx)
+            ref = msg
+        rm.recover(rx, out=llr)
+        decoder.plan.decode(llr, out, its)
+        _native.count_errors(ref, out, kf, counts)
+        return counts.cpu().numpy()
+
+    return fn
+
+
+def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encoder=None, rate_matcher=None):
     """Round function for BPDecoder / MSDecoder / LayeredMSDecoder (any decoder
     with `.plan`, `.n` and `.m`).
 
@@ -257,7 +303,16 @@ def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encod
     (decoded[:k]).  encoder = an LDPCEncoder: random k-bit messages (device
     Philox), valid codewords on the device (LDPCEncoder.encode_batch_device,
     pl_gf2_encode), errors over the encoder's info positions -- the whole Monte
-    Carlo chain device-resident."""
+    Carlo chain device-resident.
+
+    rate_matcher = a ldpc.QCRateMatcher: only E bits of each frame cross the
+    channel.  `decoder` is built on rate_matcher.decoder_base(), `encoder` (a
+    QCLDPCEncoder of the whole code, or None) encodes random messages whose
+    filler tail is zero; then select, AWGN over E, recover into the decoder's
+    dtype, decode, errors over the first k - fillers positions (`info_bits` is
+    not used).  With the all-zero codeword encode and select are skipped."""
+    if rate_matcher is not None:
+        return _rate_matched_round_fn(decoder, seed, encoder, rate_matcher)
     import torch
     from .. import _native
     from ..channel.awgn import AWGNChannel

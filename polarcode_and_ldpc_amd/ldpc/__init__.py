@@ -5,9 +5,10 @@ from .matrix import (calculate_girth, check_matrix_rank, create_systematic_gener
                      generate_ldpc_matrix, gf2_systematic_pair, layer_schedule, mackay_construction, peg_construction,
                      qc_block_layers, qc_encodable_base, qc_encoding_structure, qc_expand, qc_random_base, qc_to_csr,
                      regular_construction)
+from .ratematch import QCRateMatcher
 from .utils import calculate_syndrome, check_syndrome, count_errors, create_tanner_graph, hamming_distance
 
-__all__ = ["BPDecoder", "MSDecoder", "LayeredMSDecoder", "QCLayeredMSDecoder", "LDPCEncoder", "QCLDPCEncoder", "dense_to_csr", "csr_to_dense",
+__all__ = ["BPDecoder", "MSDecoder", "LayeredMSDecoder", "QCLayeredMSDecoder", "LDPCEncoder", "QCLDPCEncoder", "QCRateMatcher", "dense_to_csr", "csr_to_dense",
            "generate_ldpc_matrix", "mackay_construction", "regular_construction", "peg_construction",
            "layer_schedule", "create_systematic_generator", "check_matrix_rank", "calculate_girth",
            "gf2_systematic_pair", "create_tanner_graph", "check_syndrome", "calculate_syndrome", "count_errors",
