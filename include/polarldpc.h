@@ -59,7 +59,11 @@ typedef struct {
                            12 quasi-cyclic layered min-sum with its state in the
                            workspace,
                            13 / 14 the same two with the state in single precision
-                           (PL_LDPC_QC_F32)                                         */
+                           (PL_LDPC_QC_F32),
+                           15 int8 fixed-point quasi-cyclic layered min-sum with its
+                           state in LDS, 16 with its state in the workspace (such a
+                           plan reports in fused_top the kernel instance: 8, 16 or 32
+                           inputs of a check kept in registers, 0 the two-pass form) */
 } pl_plan_info;
 
 /* Polar SC / SCL plan.
@@ -185,6 +189,58 @@ int pl_ldpc_qc_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shi
                            const int32_t* layer_order /* [mb] or NULL */, int32_t max_iter, int32_t early_stop,
                            double normalization, int32_t flags, pl_plan** out);
 
+/* int8 fixed-point quasi-cyclic layered normalised min-sum plan.  Build-defined.
+ *   The code (mb, nb, z, shift), the layers (layer_order), the position j of an
+ *   input in its check (the rank of its block column among the row's non-zero
+ *   blocks), the skipping of block rows without blocks and max_iter == 0 are
+ *   exactly pl_ldpc_qc_plan_create's.  Parameters: norm16 in 1 .. 16 (the
+ *   normalisation is norm16 / 16), llr_max in 1 .. 127, msg_max in 1 .. 127.
+ *   All arithmetic is on integers and no intermediate overflows (|values| <= 254):
+ *     P[v] = clamp(L[v], -llr_max, llr_max)      L int8, any of its 256 values
+ *                                                (so -128 -> -llr_max)
+ *     R[c][j] = 0
+ *     for it < max_iter: for each block row in layer_order (d >= 2 blocks), for
+ *                        each of its z checks c:
+ *         q[j]    = clamp(P[v_j] - R[c][j], -127, 127)
+ *         mag_j   = min(msg_max, (min_{k != j} |q[k]| * norm16) >> 4)
+ *         R[c][j] = (odd number of k != j with q[k] < 0) ? -mag_j : mag_j
+ *         P[v_j]  = clamp(q[j] + R[c][j], -127, 127)
+ *       decoded = P <= 0; with early_stop, stop once every parity is even
+ *       (iterations = it + 1)
+ *   A zero q[k] counts as non-negative; its sign never shows, because it makes
+ *   the minimum 0.  No NaN, no signed zero, no rounding: bits, iteration counts
+ *   and posteriors equal a NumPy integer restatement exactly.  With norm16 = 16,
+ *   msg_max = 127 and inputs for which no clamp ever acts this is the fp64
+ *   decoder of pl_ldpc_qc_plan_create at normalisation 1.0 on the same integers.
+ *   Checks: pl_ldpc_qc_plan_create's in its order, with norm16, llr_max and msg_max
+ *   (PL_EINVAL, in this order, the message names the first one violated) behind
+ *   the layer_order check and in front of the PL_EUNSUPPORTED ones (a one-block
+ *   row when max_iter > 0, >= 2048 blocks in a row, z > 1024).  Every argument
+ *   check runs before the first device call.
+ *   Mapping as pl_ldpc_qc_plan_create's.  State per frame, mw u32 words per check
+ *   and then the posteriors.  With min1 <= min2 the two smallest |q| of a check,
+ *   s1 = min(msg_max, min1 norm16 >> 4), s2 the same of min2, idx1 the position
+ *   of min1 (the first on a tie), maxdc the largest row degree of the code:
+ *     at 0         [m][mw] u32.
+ *                  maxdc <= 14, mw = 1: s1 in bits 0-6, s2 in bits 7-13, idx1 in
+ *                  bits 14-17, the negative flags in bits 18-31 (position j at bit
+ *                  18 + j); the parity of the negative inputs is their popcount.
+ *                  maxdc > 14, mw = 1 + ceil(maxdc / 32): word 0 = s1 in bits 0-7,
+ *                  s2 in bits 8-15, idx1 in bits 16-26, the parity in bit 27;
+ *                  words 1 ..: the negative flags, position j at bit j % 32 of
+ *                  word 1 + j / 32.
+ *                  R[c][j] = +- (j == idx1 ? s2 : s1), negative iff parity != flag j.
+ *     at 4 m mw    P[n] int8
+ *   4 m mw + n bytes rounded up to 16 (n + 4 m for degrees <= 14, n + 8 m up to 32), in LDS
+ *   under pl_ldpc_qc_plan_create's rules (pl_plan_info.reserved 15), else in the
+ *   workspace (16); PL_LMS_GLOBAL=1 forces the workspace.
+ *   Such a plan decodes through pl_ldpc_decode_i8 only: pl_decode, pl_decode_ws,
+ *   pl_ldpc_decode_soft and pl_ldpc_decode_f32 return PL_EUNSUPPORTED.
+ *   pl_plan_workspace_bytes, pl_plan_reserve and pl_plan_release work as for any plan. */
+int pl_ldpc_qc_fixed_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift /* [mb*nb] row-major */,
+                                 const int32_t* layer_order /* [mb] or NULL */, int32_t max_iter, int32_t early_stop,
+                                 int32_t norm16, int32_t llr_max, int32_t msg_max, pl_plan** out);
+
 /* Batched decode: replaces SCDecoder.decode (decoder.py:38-71),
  *   SCLDecoder.decode (:225-262), BPDecoder.decode (src/ldpc/decoder.py:124-202)
  *   and MSDecoder.decode (:289-352) applied to `batch` frames.
@@ -238,6 +294,30 @@ int pl_ldpc_decode_f32(pl_plan* plan, const float* llr_dev, int64_t batch, int64
                        void* workspace_dev /* NULL: the plan's per-stream workspace */, int64_t workspace_bytes,
                        void* stream);
 
+/* Decode of a fixed-point plan (pl_ldpc_qc_fixed_plan_create): llr_dev int8
+ * [batch][ld]; post_dev int8 [batch][ld_post], ld_post >= n, the final P, or NULL;
+ * workspace_dev NULL: the plan's per-stream workspace as pl_decode, else a
+ * caller-owned one of workspace_bytes, aligned to 16 bytes, as pl_decode_ws (no
+ * allocation, so safe inside hipGraph capture).  The other arguments as pl_decode.
+ * PL_EUNSUPPORTED for every other plan. */
+int pl_ldpc_decode_i8(pl_plan* plan, const int8_t* llr_dev, int64_t batch, int64_t ld, uint8_t* bits_dev,
+                      int32_t* iters_dev, int8_t* post_dev /* may be NULL */, int64_t ld_post,
+                      void* workspace_dev /* NULL: the plan's per-stream workspace */, int64_t workspace_bytes,
+                      void* stream);
+
+/* The LLR quantiser in front of pl_ldpc_decode_i8:
+ *     out[b][v] = clamp(rint((double)llr[b][v] * scale), -llr_max, llr_max)   as int8
+ * rint rounds half to even; the input is fp64, or fp32 (PL_QUANT_LLR_F32) widened
+ * exactly; the product is one fp64 multiplication; NaN -> 0, +-inf -> +-llr_max.
+ * llr_dev [batch][ld], out_dev int8 [batch][ld_out], pitches in elements, any
+ * pitch >= n and any out_dev address (16-byte stores where the addresses allow).
+ * PL_EINVAL: unknown flag bits, batch < 0, n < 1, a scale that is not a finite
+ * double > 0, llr_max outside 1 .. 127, a pitch < n, and for batch > 0 a NULL
+ * pointer or an llr_dev not aligned to its element type.  batch == 0 does nothing. */
+#define PL_QUANT_LLR_F32 1
+int pl_llr_quantize(const void* llr_dev, int32_t flags, int64_t ld, int64_t batch, int32_t n, double scale,
+                    int32_t llr_max, int8_t* out_dev, int64_t ld_out, void* stream);
+
 /* Pre-allocate `stream`'s workspace for batches up to max_batch, so that
  * pl_decode on that stream never allocates (max_batch == 0: pl_plan_release).
  * If the device cannot hold the full-speed size, the largest halving of at
@@ -267,7 +347,7 @@ int pl_plan_destroy(pl_plan* plan);
 const char* pl_last_error(void);
 
 /* Calls that touch a plan's device memory -- pl_decode, pl_decode_ws,
- * pl_ldpc_decode_soft, pl_ldpc_decode_f32, pl_plan_reserve, pl_plan_release, pl_polar_plan_set_crc, pl_polar_encode,
+ * pl_ldpc_decode_soft, pl_ldpc_decode_f32, pl_ldpc_decode_i8, pl_plan_reserve, pl_plan_release, pl_polar_plan_set_crc, pl_polar_encode,
  * pl_debug_polar_stamps -- must run with the plan's device current (the device
  * current at plan creation); otherwise they return PL_EINVAL and do nothing.
  * pl_plan_get_info, pl_plan_workspace_bytes and pl_plan_workspace_stats read
@@ -389,6 +469,22 @@ int pl_debug_ldpc_qc_plan_probe_flags(int32_t mb, int32_t nb, int32_t z, const i
                                       const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
                                       double normalization, int32_t lms_global, int32_t flags,
                                       pl_ldpc_qc_plan_probe* out);
+
+/* The same for pl_ldpc_qc_fixed_plan_create: the fields of pl_ldpc_qc_plan_probe
+ * with the plan's three parameters, and off_p, the byte offset of P behind the
+ * check words (state_bytes = off_p + n rounded up to 16). */
+typedef struct {
+    int32_t kernel;      /* 15 or 16, as pl_plan_info.reserved */
+    int32_t z, mb, nb, maxdc, dcap, mw, fpw, fpb, threads, lds_bytes, use_global;
+    int32_t norm16, llr_max, msg_max, pad;
+    int64_t state_bytes, off_p;
+    int64_t table_len;
+    uint64_t digest;
+} pl_ldpc_qc_fixed_plan_probe;
+int pl_debug_ldpc_qc_fixed_plan_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                      const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
+                                      int32_t norm16, int32_t llr_max, int32_t msg_max, int32_t lms_global,
+                                      pl_ldpc_qc_fixed_plan_probe* out);
 
 /* ---- Monte-Carlo frame source (replaces src/channel/awgn.py:91-112 and the
  *      message/encode loop of benchmarks/ber_simulation.py:167-177) ---------- */

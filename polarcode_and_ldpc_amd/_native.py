@@ -31,8 +31,10 @@ EXPORTS = (
     "pl_debug_ldpc_qc_plan_probe", "pl_ldpc_decode_f32", "pl_debug_ldpc_qc_plan_probe_flags",
     "pl_ldpc_qc_encoder_create", "pl_ldpc_qc_encode", "pl_ldpc_qc_encoder_destroy", "pl_debug_ldpc_qc_encoder_probe",
     "pl_debug_set_qc_encoder_device", "pl_ldpc_rate_match_check", "pl_debug_rate_match_probe", "pl_ldpc_rate_match",
-    "pl_ldpc_rate_recover",
+    "pl_ldpc_rate_recover", "pl_ldpc_qc_fixed_plan_create", "pl_ldpc_decode_i8", "pl_llr_quantize",
+    "pl_debug_ldpc_qc_fixed_plan_probe",
 )
+PL_QUANT_LLR_F32 = 1  # pl_llr_quantize flag: llr_dev is float (else double)
 PL_RM_LLR_F32, PL_RM_OUT_F32, PL_RM_ACCUMULATE = 1, 2, 4  # pl_ldpc_rate_recover flags
 
 
@@ -63,6 +65,14 @@ class LdpcQcPlanProbe(ctypes.Structure):
     _fields_ = [(f, ctypes.c_int32) for f in ("kernel", "z", "mb", "nb", "maxdc", "dcap", "mw", "fpw", "fpb", "threads",
                                               "lds_bytes", "use_global")] + \
                [(f, ctypes.c_int64) for f in ("state_bytes", "table_len")] + \
+               [("digest", ctypes.c_uint64)]
+
+
+class LdpcQcFixedPlanProbe(ctypes.Structure):
+    """pl_ldpc_qc_fixed_plan_probe: the fixed-point quasi-cyclic kernel's geometry."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("kernel", "z", "mb", "nb", "maxdc", "dcap", "mw", "fpw", "fpb", "threads",
+                                              "lds_bytes", "use_global", "norm16", "llr_max", "msg_max", "pad")] + \
+               [(f, ctypes.c_int64) for f in ("state_bytes", "off_p", "table_len")] + \
                [("digest", ctypes.c_uint64)]
 
 
@@ -98,6 +108,11 @@ def _load(path=LIB_PATH):
     L.pl_debug_ldpc_qc_plan_probe.argtypes = [I32, I32, I32, P, P, I32, I32, D, I32, ctypes.POINTER(LdpcQcPlanProbe)]
     L.pl_debug_ldpc_qc_plan_probe_flags.argtypes = [I32, I32, I32, P, P, I32, I32, D, I32, I32,
                                                     ctypes.POINTER(LdpcQcPlanProbe)]
+    L.pl_ldpc_qc_fixed_plan_create.argtypes = [I32, I32, I32, P, P, I32, I32, I32, I32, I32, PP]
+    L.pl_debug_ldpc_qc_fixed_plan_probe.argtypes = [I32, I32, I32, P, P, I32, I32, I32, I32, I32, I32,
+                                                    ctypes.POINTER(LdpcQcFixedPlanProbe)]
+    L.pl_ldpc_decode_i8.argtypes = [P, P, I64, I64, P, P, P, I64, P, I64, P]
+    L.pl_llr_quantize.argtypes = [P, I32, I64, I64, I32, D, I32, P, I64, P]
     L.pl_ldpc_qc_encoder_create.argtypes = [I32, I32, I32, P, PP]
     L.pl_ldpc_qc_encode.argtypes = [P, P, I64, I64, P, I64, P]
     L.pl_ldpc_qc_encoder_destroy.argtypes = [P]
@@ -209,6 +224,8 @@ class Plan:
         self.info = info
         # a quasi-cyclic plan created with PL_LDPC_QC_F32 (it also takes fp32 llr / post); fixed at creation
         self.f32 = info.reserved in (13, 14)
+        # an int8 fixed-point plan (pl_ldpc_qc_fixed_plan_create): int8 llr / post through pl_ldpc_decode_i8 only
+        self.fixed = info.reserved in (15, 16)
 
     @property
     def handle(self):
@@ -243,7 +260,9 @@ class Plan:
         # the kernels write bits at row pitch n_out and iters densely; llr rows
         # may carry any pitch >= n_in but unit inner stride
         assert isinstance(llr, torch.Tensor) and llr.is_cuda, "llr must be a device tensor"
-        if llr.dtype == torch.float32:
+        if self.fixed or llr.dtype == torch.int8:
+            assert self.fixed and llr.dtype == torch.int8, "int8 llr and fixed-point plans go together only"
+        elif llr.dtype == torch.float32:
             assert self.f32, "fp32 llr: quasi-cyclic plans created with PL_LDPC_QC_F32 only"
         else:
             assert llr.dtype == torch.float64
@@ -258,7 +277,8 @@ class Plan:
                ws: "torch.Tensor | None" = None):
         """llr fp64 [B, >=n_in] device, bits uint8 [B, n_out] contiguous, iters int32 [B]
         or None; ws: optional caller-owned uint8 device workspace (pl_decode_ws).
-        A PL_LDPC_QC_F32 plan also takes fp32 llr (pl_ldpc_decode_f32)."""
+        A PL_LDPC_QC_F32 plan also takes fp32 llr (pl_ldpc_decode_f32); a fixed-point
+        plan takes int8 llr only (pl_ldpc_decode_i8)."""
         self._check(llr, bits, iters)
         assert ws is None or (ws.is_cuda and ws.is_contiguous())
         self._decode(llr, bits, iters, None, ws, stream)
@@ -273,7 +293,9 @@ class Plan:
         soft = (None, 0) if post is None else (post.data_ptr(), _ld(post))
         work = (None, 0) if ws is None else (ws.data_ptr(), ws.numel() * ws.element_size())
         st = _stream(stream)
-        if llr.dtype == torch.float32:
+        if llr.dtype == torch.int8:
+            check(lib.pl_ldpc_decode_i8(*head, *soft, *work, st), "pl_ldpc_decode_i8")
+        elif llr.dtype == torch.float32:
             check(lib.pl_ldpc_decode_f32(*head, *soft, *work, st), "pl_ldpc_decode_f32")
         elif post is not None:
             check(lib.pl_ldpc_decode_soft(*head, *soft, st), "pl_ldpc_decode_soft")
@@ -291,8 +313,8 @@ class Plan:
         self._check(llr, bits, iters)
         assert post.is_cuda and post.dtype == llr.dtype and post.dim() == 2 and post.stride(1) == 1 \
             and post.shape[0] == llr.shape[0] and post.shape[1] >= self.info.n_in, \
-            "post must be a [B, >=n] device tensor of llr's dtype (float64; float32 on a PL_LDPC_QC_F32 plan) " \
-            "with unit inner stride"
+            "post must be a [B, >=n] device tensor of llr's dtype (float64; float32 on a PL_LDPC_QC_F32 plan; " \
+            "int8 on a fixed-point plan) with unit inner stride"
         self._decode(llr, bits, iters, post, None, stream)
 
     def decode_stamped(self, llr: "torch.Tensor", bits: "torch.Tensor", stamps: "torch.Tensor", stream=None):
@@ -382,6 +404,35 @@ def qc_ldpc_plan(base: np.ndarray, Z: int, layer_order, max_iter: int, early_sto
                                      int(bool(early_stop)), float(normalization), int(flags), ctypes.byref(h)),
           "pl_ldpc_qc_plan_create")
     return Plan(h)
+
+
+def qc_fixed_ldpc_plan(base: np.ndarray, Z: int, layer_order, max_iter: int, early_stop: bool, norm16: int,
+                       llr_max: int, msg_max: int) -> Plan:
+    """int8 fixed-point quasi-cyclic layered min-sum plan (pl_ldpc_qc_fixed_plan_create); base and
+    layer_order as qc_ldpc_plan's."""
+    sh = np.ascontiguousarray(base, dtype=np.int32)
+    assert sh.ndim == 2, "base must be [mb, nb]"
+    lo = None if layer_order is None else np.ascontiguousarray(layer_order, dtype=np.int32).ravel()
+    assert lo is None or len(lo) == sh.shape[0], "layer_order must list the mb block rows"
+    require_gpu()
+    h = ctypes.c_void_p()
+    check(lib.pl_ldpc_qc_fixed_plan_create(sh.shape[0], sh.shape[1], int(Z), sh.ctypes.data_as(ctypes.c_void_p),
+                                           None if lo is None else lo.ctypes.data_as(ctypes.c_void_p), int(max_iter),
+                                           int(bool(early_stop)), int(norm16), int(llr_max), int(msg_max),
+                                           ctypes.byref(h)), "pl_ldpc_qc_fixed_plan_create")
+    return Plan(h)
+
+
+def llr_quantize(llr: "torch.Tensor", scale: float, llr_max: int, out: "torch.Tensor", stream=None):
+    """pl_llr_quantize: llr float64 or float32 [B, >= n], out int8 [B, >= n] with n = out.shape[1]: device
+    tensors (or views) with unit inner stride, any row pitch."""
+    assert llr.dtype in (torch.float64, torch.float32) and out.dtype == torch.int8
+    assert llr.dim() == 2 and out.dim() == 2 and llr.shape[0] == out.shape[0] and llr.shape[1] >= out.shape[1]
+    if out.shape[0] == 0:
+        return
+    check(lib.pl_llr_quantize(_dptr(llr), PL_QUANT_LLR_F32 if llr.dtype == torch.float32 else 0, _ld(llr),
+                              llr.shape[0], out.shape[1], float(scale), int(llr_max), _dptr(out), _ld(out),
+                              _stream(stream)), "pl_llr_quantize")
 
 
 class QcEncoder:

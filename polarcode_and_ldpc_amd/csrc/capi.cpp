@@ -86,6 +86,10 @@ struct pl_plan {
     bool qc = false;
     bool qc_f32 = false;  // created with PL_LDPC_QC_F32: state and arithmetic in single precision
     pl::QcGeom qcg{};
+    // int8 fixed-point quasi-cyclic layered min-sum (ldpc_qc_fixed.hip): a layered plan (lms.n, lms.m set)
+    // that only pl_ldpc_decode_i8 decodes; its table buffer is the layer stream
+    bool qc_fixed = false;
+    pl::QcFixedGeom qfg{};
     // workspace: bytes per unit (polar: one resident wave; LDPC global: one
     // frame), one buffer per stream (plans are shared across host threads that
     // use distinct streams; a decode only ever touches its stream's buffer)
@@ -429,6 +433,31 @@ extern "C" int pl_ldpc_qc_plan_create(int32_t mb, int32_t nb, int32_t z, const i
     return PL_OK;
 }
 
+extern "C" int pl_ldpc_qc_fixed_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                            const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
+                                            int32_t norm16, int32_t llr_max, int32_t msg_max, pl_plan** out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    *out = nullptr;
+    // every argument check (ldpc_plan.cpp) comes before the first device call
+    pl::QcFixedHostPlan hp;
+    const pl::PlanStatus st = pl::qc_fixed_plan_build(mb, nb, z, shift, layer_order, max_iter, early_stop, norm16,
+                                                      llr_max, msg_max, ldpc_env_options(), &hp);
+    if (st.code) return fail(st.code, st.msg);
+    PlanPtr plan;
+    if (int rc = ldpc_plan_upload(hp.tables, &plan)) return rc;
+    pl_plan* const p = plan.get();
+    p->layered = true;
+    p->qc_fixed = true;
+    p->qfg = hp.geom;
+    p->lg.n = p->lms.n = hp.geom.n;
+    p->lg.m = p->lms.m = hp.geom.m;
+    const hipError_t e = pl::qc_fixed_prepare(p->qfg);
+    if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute");
+    p->ws_unit = p->qfg.use_global ? (size_t)p->qfg.state_bytes : 0;
+    *out = plan.release();
+    return PL_OK;
+}
+
 // The planner's decisions for a code, with no plan object and no device call.
 extern "C" int pl_debug_ldpc_plan_probe(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
                                         int32_t algo, int32_t max_iter, int32_t early_stop, double normalization,
@@ -489,6 +518,23 @@ extern "C" int pl_debug_ldpc_qc_plan_probe(int32_t mb, int32_t nb, int32_t z, co
                                            double normalization, int32_t lms_global, pl_ldpc_qc_plan_probe* out) {
     return pl_debug_ldpc_qc_plan_probe_flags(mb, nb, z, shift, layer_order, max_iter, early_stop, normalization,
                                              lms_global, 0, out);
+}
+
+extern "C" int pl_debug_ldpc_qc_fixed_plan_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                                 const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
+                                                 int32_t norm16, int32_t llr_max, int32_t msg_max, int32_t lms_global,
+                                                 pl_ldpc_qc_fixed_plan_probe* out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    pl::QcFixedHostPlan hp;
+    const pl::PlanStatus st = pl::qc_fixed_plan_build(mb, nb, z, shift, layer_order, max_iter, early_stop, norm16,
+                                                      llr_max, msg_max, ldpc_options(0, 0, lms_global), &hp);
+    if (st.code) return fail(st.code, st.msg);
+    const pl::QcFixedGeom& g = hp.geom;
+    *out = pl_ldpc_qc_fixed_plan_probe{pl::qc_fixed_kernel_code(g), g.z, g.mb, g.nb, g.maxdc, g.dcap, g.mw, g.fpw,
+                                       g.fpb, g.threads, g.lds_bytes, g.use_global, g.norm16, g.llr_max, g.msg_max,
+                                       0, g.state_bytes, g.off_p, (int64_t)hp.tables.size(),
+                                       pl::plan_tables_digest(hp.tables)};
+    return PL_OK;
 }
 
 // Polar workspace layout for a grid of `grid` resident wavefronts: a list
@@ -720,8 +766,14 @@ static int decode_on_stream(pl_plan* p, const double* llr, int64_t batch, int64_
     });
 }
 
-static int check_decode_args(const pl_plan* p, int64_t batch, int64_t ld, const void* llr, const void* bits) {
+static const char kFixedOnly[] =
+    "a fixed-point plan (pl_ldpc_qc_fixed_plan_create) decodes int8 LLRs through pl_ldpc_decode_i8 only";
+
+// i8: the call is pl_ldpc_decode_i8's; every floating-point entry point refuses a fixed-point plan
+static int check_decode_args(const pl_plan* p, int64_t batch, int64_t ld, const void* llr, const void* bits,
+                             bool i8 = false) {
     if (!p) return fail(PL_EINVAL, "plan is NULL");
+    if (p->qc_fixed && !i8) return fail(PL_EUNSUPPORTED, kFixedOnly);
     if (batch < 0) return fail(PL_EINVAL, "batch < 0");
     if (batch > 0 && (!llr || !bits)) return fail(PL_EINVAL, "NULL buffer");
     if (p->kind == 0 && ld < p->pg.N) return fail(PL_EINVAL, "ld < N");
@@ -823,6 +875,7 @@ extern "C" int pl_ldpc_decode_f32(pl_plan* p, const float* llr, int64_t batch, i
                                   int32_t* iters, float* post, int64_t ld_post, void* workspace,
                                   int64_t workspace_bytes, void* stream) {
     if (!p) return fail(PL_EINVAL, "plan is NULL");
+    if (p->qc_fixed) return fail(PL_EUNSUPPORTED, kFixedOnly);
     if (!p->qc || !p->qc_f32)
         return fail(PL_EUNSUPPORTED, "fp32 LLRs: quasi-cyclic plans created with PL_LDPC_QC_F32 only");
     int rc = check_decode_args(p, batch, ld, llr, bits);
@@ -837,6 +890,61 @@ extern "C" int pl_ldpc_decode_f32(pl_plan* p, const float* llr, int64_t batch, i
     return with_stream_ws(p, s, ws_need(p, batch), [&](void* ws, size_t bytes) {
         return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, ws, bytes, s);
     });
+}
+
+// pl_ldpc_decode_i8's launches: lms_decode_impl's chunking on the fixed-point kernel
+static int fixed_decode_impl(pl_plan* p, const int8_t* llr, int64_t batch, int64_t ld, uint8_t* bits, int32_t* iters,
+                             int8_t* post, int64_t ld_post, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (p->ws_unit > 0 && (ws == nullptr || ws_bytes < p->ws_unit))
+        return fail(PL_EINVAL, "workspace smaller than one unit (pl_plan_workspace_bytes)");
+    if (p->ws_unit > 0 && ((uintptr_t)ws & 15))
+        return fail(PL_EINVAL, "workspace must be aligned to 16 bytes");
+    const int64_t step = p->ws_unit > 0 ? std::min<int64_t>(p->ldpc_chunk, (int64_t)(ws_bytes / p->ws_unit))
+                                        : kMaxLaunchItems / 1024;
+    return for_chunks(batch, step, [&](int64_t b0, int64_t nb) {
+        const hipError_t e = pl::qc_fixed_launch(p->qfg, p->d_ldpc, llr + b0 * ld, ld, bits + b0 * p->lms.n,
+                                                 iters ? iters + b0 : nullptr, post ? post + b0 * ld_post : nullptr,
+                                                 ld_post, nb, (unsigned char*)ws, s);
+        return e == hipSuccess ? PL_OK : hipfail(e, "fixed-point ldpc decode launch");
+    });
+}
+
+extern "C" int pl_ldpc_decode_i8(pl_plan* p, const int8_t* llr, int64_t batch, int64_t ld, uint8_t* bits,
+                                 int32_t* iters, int8_t* post, int64_t ld_post, void* workspace,
+                                 int64_t workspace_bytes, void* stream) {
+    if (!p) return fail(PL_EINVAL, "plan is NULL");
+    if (!p->qc_fixed)
+        return fail(PL_EUNSUPPORTED, "int8 LLRs: fixed-point plans (pl_ldpc_qc_fixed_plan_create) only");
+    int rc = check_decode_args(p, batch, ld, llr, bits, true);
+    if (rc) return rc;
+    if (post && ld_post < p->lms.n) return fail(PL_EINVAL, "ld_post < n");
+    if (workspace && workspace_bytes < 0) return fail(PL_EINVAL, "workspace_bytes < 0");
+    if (batch == 0) return PL_OK;
+    if ((rc = check_device(p))) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (workspace)
+        return fixed_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, workspace, (size_t)workspace_bytes, s);
+    return with_stream_ws(p, s, ws_need(p, batch), [&](void* ws, size_t bytes) {
+        return fixed_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, ws, bytes, s);
+    });
+}
+
+extern "C" int pl_llr_quantize(const void* llr, int32_t flags, int64_t ld, int64_t batch, int32_t n, double scale,
+                               int32_t llr_max, int8_t* out, int64_t ld_out, void* stream) {
+    if (flags & ~PL_QUANT_LLR_F32) return fail(PL_EINVAL, "unknown flag bits");
+    if (batch < 0) return fail(PL_EINVAL, "batch must be >= 0");
+    if (n < 1) return fail(PL_EINVAL, "n must be >= 1");
+    if (!(scale > 0.0) || !std::isfinite(scale)) return fail(PL_EINVAL, "scale must be finite and > 0");
+    if (llr_max < 1 || llr_max > 127) return fail(PL_EINVAL, "llr_max = " + std::to_string(llr_max) + " outside 1 .. 127");
+    if (ld < n) return fail(PL_EINVAL, "ld < n");
+    if (ld_out < n) return fail(PL_EINVAL, "ld_out < n");
+    if (batch == 0) return PL_OK;
+    if (!llr || !out) return fail(PL_EINVAL, "device pointers must not be NULL");
+    if ((uintptr_t)llr & ((flags & PL_QUANT_LLR_F32) ? 3 : 7))
+        return fail(PL_EINVAL, "llr_dev must be aligned to its element type");
+    const hipError_t e = pl::llr_quantize_launch(llr, flags & PL_QUANT_LLR_F32, ld, batch, n, scale, llr_max, out,
+                                                 ld_out, (hipStream_t)stream);
+    return e == hipSuccess ? PL_OK : hipfail(e, "llr quantize launch");
 }
 
 extern "C" int pl_debug_polar_stamps(pl_plan* p, const double* llr, int64_t batch, int64_t ld, uint8_t* bits,
@@ -981,6 +1089,11 @@ extern "C" int pl_plan_get_info(const pl_plan* p, pl_plan_info* info) {
         if (p->qc) {  // quasi-cyclic layered min-sum: 11 state in LDS, 12 in the workspace; fp32 state: 13, 14
             info->lds_bytes = p->qcg.lds_bytes; info->frames_per_block = p->qcg.fpw * p->qcg.fpb;
             info->reserved = pl::qc_kernel_code(p->qcg, p->qc_f32);
+        }
+        if (p->qc_fixed) {  // int8 fixed-point quasi-cyclic layered min-sum: 15 state in LDS, 16 in the workspace
+            info->lds_bytes = p->qfg.lds_bytes; info->frames_per_block = p->qfg.fpw * p->qfg.fpb;
+            info->fused_top = p->qfg.dcap;  // the instance: inputs of a check kept in registers, 0 the two-pass form
+            info->reserved = pl::qc_fixed_kernel_code(p->qfg);
         }
     } else {
         info->kind = 1; info->n_in = p->lg.n; info->n_out = p->lg.n; info->list_size = 0;

@@ -144,6 +144,16 @@ hipError_t qc_launch(const QcGeom& g, bool f32, const int32_t* tab, const double
 hipError_t qc_launch(const QcGeom& g, const int32_t* tab, const float* llr, int64_t ld, uint8_t* bits, int32_t* iters,
                      float* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
 
+// ---- int8 fixed-point quasi-cyclic layered min-sum and the LLR quantiser (ldpc_qc_fixed.hip) ----
+hipError_t qc_fixed_prepare(const QcFixedGeom& g);
+// llr int8 [batch][ld]; post int8 [batch][ld_post] or null; the other arguments as qc_launch
+hipError_t qc_fixed_launch(const QcFixedGeom& g, const int32_t* tab, const int8_t* llr, int64_t ld, uint8_t* bits,
+                           int32_t* iters, int8_t* post, int64_t ld_post, int64_t batch, unsigned char* work,
+                           hipStream_t s);
+// llr [batch][ldi] double, or float with f32; out int8 [batch][ldo]; chunks its launches itself
+hipError_t llr_quantize_launch(const void* llr, bool f32, int64_t ldi, int64_t batch, int n, double scale, int llr_max,
+                               int8_t* out, int64_t ldo, hipStream_t s);
+
 // ---- quasi-cyclic encoder from the base matrix (ldpc_qc_encode.hip); QcEncGeom: ldpc_plan.hpp ----
 hipError_t qc_encode_prepare(const QcEncGeom& g);
 // tab: the plan's stream (device); msg uint8 [batch][ldm] (bit 0 of each byte), cw uint8 [batch][ldc]

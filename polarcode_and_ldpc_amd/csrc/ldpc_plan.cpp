@@ -428,9 +428,13 @@ PlanStatus lms_plan_build(int m, int n, const int32_t* row_ptr, const int32_t* c
 
 // ---- quasi-cyclic layered plans ----
 
-PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order, int max_iter,
-                         int early_stop, double norm, const LdpcPlanOptions& opt, QcHostPlan* out) {
-    constexpr int kLdsMax = 160 * 1024;
+// The fixed-point plan's three parameters (qc_fixed_plan_build); null for the floating-point plans.
+struct QcFixedParams { int norm16, llr_max, msg_max; };
+
+// The checks of a quasi-cyclic layered plan, in the order the header documents, then the layer stream.
+static PlanStatus qc_check_and_stream(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order,
+                                      int max_iter, const QcFixedParams* fx, int* maxdc_out,
+                                      std::vector<int32_t>* tables) {
     if (mb < 1 || nb < 1 || z < 1 || !shift) return refuse(PL_EINVAL, "mb, nb and Z must be >= 1");
     if ((int64_t)nb * z > INT32_MAX || (int64_t)mb * z > INT32_MAX)
         return refuse(PL_EINVAL, "nb Z and mb Z must fit 32 bits");
@@ -463,11 +467,67 @@ PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int3
     } else {
         for (int l = 0; l < mb; ++l) order[l] = l;
     }
+    if (fx) {
+        const auto S = [](int v) { return std::to_string(v); };
+        if (fx->norm16 < 1 || fx->norm16 > 16) return refuse(PL_EINVAL, "norm16 = " + S(fx->norm16) + " outside 1 .. 16");
+        if (fx->llr_max < 1 || fx->llr_max > 127)
+            return refuse(PL_EINVAL, "llr_max = " + S(fx->llr_max) + " outside 1 .. 127");
+        if (fx->msg_max < 1 || fx->msg_max > 127)
+            return refuse(PL_EINVAL, "msg_max = " + S(fx->msg_max) + " outside 1 .. 127");
+    }
     // max_iter == 0 evaluates no check, as in the layered plan
     if (deg1 && max_iter > 0)
         return refuse(PL_EUNSUPPORTED, "min-sum on a degree-1 check (reference raises ValueError)");
     if (maxdc >= (1 << 11)) return refuse(PL_EUNSUPPORTED, "check degree >= 2048");
     if (z > kQcMaxZ) return refuse(PL_EUNSUPPORTED, "Z > 1024");
+
+    std::vector<int32_t>& t = *tables;
+    t.clear();
+    t.reserve(2 * (size_t)mb + 2 * blocks);
+    for (int l = 0; l < mb; ++l) {
+        const int i = order[l];
+        const size_t at = t.size();
+        t.push_back(i);
+        t.push_back(0);
+        for (int j = 0; j < nb; ++j) {
+            const int s = shift[(size_t)i * nb + j];
+            if (s >= 0) { t.push_back(j); t.push_back(s); }
+        }
+        t[at + 1] = (int32_t)((t.size() - at - 2) / 2);
+    }
+    *maxdc_out = maxdc;
+    return {};
+}
+
+// Frames to lanes and the state's home, from g.z and g.state_bytes (QcGeom and QcFixedGeom name the
+// fields alike): the 160 KB bound on a workgroup's LDS and, for z <= 64, the 64 KB a wavefront's frames
+// may take before fewer than four wavefronts share a workgroup.
+template <class G>
+static void qc_map(G& g, bool force_global) {
+    constexpr int kLdsMax = 160 * 1024;
+    g.subwave = g.z <= 64 ? 1 : 0;
+    if (g.subwave) {
+        // fpw frames side by side in a wavefront's lanes; the LDS bound of lms_geom's WAVE case, per wavefront
+        g.fpw = 64 / g.z;
+        const int64_t wave_state = g.state_bytes * g.fpw;
+        g.use_global = (force_global || wave_state > kLdsMax) ? 1 : 0;
+        g.fpb = g.use_global ? 4 : (int)std::max<int64_t>(1, std::min<int64_t>(4, 65536 / wave_state));
+        g.threads = 64 * g.fpb;
+        g.lds_bytes = g.use_global ? 0 : (int)(wave_state * g.fpb);
+    } else {
+        g.fpw = 1;
+        g.fpb = 1;
+        g.use_global = (force_global || g.state_bytes + kLdpcVoteBytes > kLdsMax) ? 1 : 0;
+        g.threads = (g.z + 63) / 64 * 64;
+        g.lds_bytes = (g.use_global ? 0 : (int)g.state_bytes) + kLdpcVoteBytes;
+    }
+}
+
+PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order, int max_iter,
+                         int early_stop, double norm, const LdpcPlanOptions& opt, QcHostPlan* out) {
+    int maxdc = 0;
+    const PlanStatus st = qc_check_and_stream(mb, nb, z, shift, layer_order, max_iter, nullptr, &maxdc, &out->tables);
+    if (st.code) return st;
 
     LmsGeom lg{};  // the state layout is the layered kernel's
     lg.m = mb * z; lg.n = nb * z; lg.maxdc = maxdc; lg.max_layer = z;
@@ -486,36 +546,26 @@ PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int3
         g.off_meta = g.off_mm + (int64_t)8 * g.m;
         g.state_bytes = (int64_t)ldpc_align16((size_t)g.off_meta + (size_t)4 * g.m * g.mw);
     }
-    g.subwave = z <= 64 ? 1 : 0;
-    if (g.subwave) {
-        // fpw frames side by side in a wavefront's lanes; the LDS bound of lms_geom's WAVE case, per wavefront
-        g.fpw = 64 / z;
-        const int64_t wave_state = g.state_bytes * g.fpw;
-        g.use_global = (opt.lms_global || wave_state > kLdsMax) ? 1 : 0;
-        g.fpb = g.use_global ? 4 : (int)std::max<int64_t>(1, std::min<int64_t>(4, 65536 / wave_state));
-        g.threads = 64 * g.fpb;
-        g.lds_bytes = g.use_global ? 0 : (int)(wave_state * g.fpb);
-    } else {
-        g.fpw = 1;
-        g.fpb = 1;
-        g.use_global = (opt.lms_global || g.state_bytes + kLdpcVoteBytes > kLdsMax) ? 1 : 0;
-        g.threads = (z + 63) / 64 * 64;
-        g.lds_bytes = (g.use_global ? 0 : (int)g.state_bytes) + kLdpcVoteBytes;
-    }
-    std::vector<int32_t>& t = out->tables;
-    t.clear();
-    t.reserve(2 * (size_t)mb + 2 * blocks);
-    for (int l = 0; l < mb; ++l) {
-        const int i = order[l];
-        const size_t at = t.size();
-        t.push_back(i);
-        t.push_back(0);
-        for (int j = 0; j < nb; ++j) {
-            const int s = shift[(size_t)i * nb + j];
-            if (s >= 0) { t.push_back(j); t.push_back(s); }
-        }
-        t[at + 1] = (int32_t)((t.size() - at - 2) / 2);
-    }
+    qc_map(g, opt.lms_global);
+    return {};
+}
+
+PlanStatus qc_fixed_plan_build(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order, int max_iter,
+                               int early_stop, int norm16, int llr_max, int msg_max, const LdpcPlanOptions& opt,
+                               QcFixedHostPlan* out) {
+    const QcFixedParams fx{norm16, llr_max, msg_max};
+    int maxdc = 0;
+    const PlanStatus st = qc_check_and_stream(mb, nb, z, shift, layer_order, max_iter, &fx, &maxdc, &out->tables);
+    if (st.code) return st;
+    QcFixedGeom& g = out->geom;
+    g = QcFixedGeom{};
+    g.mb = mb; g.nb = nb; g.z = z; g.m = mb * z; g.n = nb * z; g.max_iter = max_iter; g.early_stop = early_stop ? 1 : 0;
+    g.maxdc = maxdc; g.norm16 = norm16; g.llr_max = llr_max; g.msg_max = msg_max;
+    g.dcap = maxdc <= 8 ? 8 : maxdc <= 16 ? 16 : maxdc <= kQcDcapMax ? 32 : 0;
+    g.mw = maxdc <= kQcFixedOneWord ? 1 : 1 + (maxdc + 31) / 32;
+    g.off_p = (int64_t)4 * g.m * g.mw;
+    g.state_bytes = (int64_t)ldpc_align16((size_t)g.off_p + (size_t)g.n);
+    qc_map(g, opt.lms_global);
     return {};
 }
 

@@ -225,6 +225,38 @@ struct QcHostPlan {
 PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order, int max_iter,
                          int early_stop, double norm, const LdpcPlanOptions& opt, QcHostPlan* out);
 
+// ---- int8 fixed-point quasi-cyclic layered min-sum (ldpc_qc_fixed.hip) ----
+// The definition: include/polarldpc.h, pl_ldpc_qc_fixed_plan_create.  Mapping and layer stream are
+// qc_plan_build's.  State layout per frame, all of it in LDS or all of it in the frame's workspace slice:
+//   at 0      [m][mw] u32 per check.  s1 = min(msg_max, min1 norm16 >> 4) and s2 likewise of min2, the two
+//             smallest |q| of the check; idx1 the position of min1 (the first one on a tie).
+//             maxdc <= 14, mw = 1: s1 bits 0-6, s2 bits 7-13, idx1 bits 14-17, the negative flags bits
+//               18-31 (position j at bit 18 + j); the parity of the negative inputs is their popcount
+//             maxdc > 14, mw = 1 + ceil(maxdc / 32): word 0 = s1 bits 0-7, s2 bits 8-15, idx1 bits 16-26,
+//               the parity bit 27; words 1 ..: the negative flags, position j at bit j % 32 of word 1 + j / 32
+//   at off_p = 4 m mw   P[n] int8
+//   state_bytes = align16(off_p + n): n + 4 m rounded up to 16 for degrees <= 14, n + 8 m up to 32.
+struct QcFixedGeom {
+    int mb, nb, z, m, n, max_iter, early_stop, maxdc;
+    int norm16, llr_max, msg_max;  // the normalisation in sixteenths and the two saturation bounds
+    int mw;          // u32 words per check: 1 (maxdc <= kQcFixedOneWord) or 1 + ceil(maxdc / 32)
+    int dcap;        // as QcGeom::dcap
+    int subwave, use_global, fpw, fpb, threads, lds_bytes;  // as QcGeom's
+    int64_t state_bytes, off_p;
+};
+constexpr int kQcFixedOneWord = 14;  // 7 + 7 bits of minima, 4 of idx1 and 14 flags fill a word
+inline int qc_fixed_kernel_code(const QcFixedGeom& g) { return g.use_global ? 16 : 15; }
+struct QcFixedHostPlan {
+    QcFixedGeom geom{};
+    std::vector<int32_t> tables;  // QcHostPlan::tables: the same stream for the same base matrix
+};
+// pl_ldpc_qc_fixed_plan_create's arguments.  qc_plan_build's checks in its order, with norm16 in 1 .. 16,
+// llr_max in 1 .. 127 and msg_max in 1 .. 127 (PL_EINVAL, in this order) behind the layer_order check
+// and in front of the PL_EUNSUPPORTED ones.
+PlanStatus qc_fixed_plan_build(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order, int max_iter,
+                               int early_stop, int norm16, int llr_max, int msg_max, const LdpcPlanOptions& opt,
+                               QcFixedHostPlan* out);
+
 // ---- quasi-cyclic encoder from the base matrix (ldpc_qc_encode.hip) ----
 // The supported structure and the encoding steps: include/polarldpc.h,
 // pl_ldpc_qc_encoder_create.  kb = nb - mb message block columns, then mb parity

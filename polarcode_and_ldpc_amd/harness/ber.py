@@ -15,7 +15,7 @@ max_iterations, errors over the k message positions.  LDPC frames use the
 all-zero codeword (BP is codeword-symmetric) or, on request, random messages
 through a device encoder; polar frames use random messages through the device
 encoder.  simulate_qc_ldpc is the same for a quasi-cyclic code given by its base
-matrix (layered min-sum, fp64 or fp32; codewords from QCLDPCEncoder).
+matrix (layered min-sum, fp64, fp32 or int8 fixed point; codewords from QCLDPCEncoder).
 """
 from __future__ import annotations
 
@@ -99,7 +99,8 @@ def simulate_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: in
 
 def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: int, base, Z: int,
                      max_iter: int = 20, normalization: float = 0.75, dtype=np.float64, batch: int = 65536,
-                     seed: int = 0, group=None, random_codewords: bool = False, log_path=None, rate_match=None):
+                     seed: int = 0, group=None, random_codewords: bool = False, log_path=None, rate_match=None,
+                     fixed=None):
     """simulate_ldpc for the quasi-cyclic code (base, Z): QCLayeredMSDecoder (layered
     normalised min-sum, early stop, state in `dtype`) on frames of the all-zero
     codeword or, random_codewords, of random messages encoded on the device from
@@ -110,34 +111,51 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
     rate_match: None, or QCRateMatcher's arguments behind (base, Z) -- a dict, or
     the sequence (E, punctured, fillers[, ncb[, start]]): E bits of each frame are
     transmitted (ldpc_round_fn's rate_matcher), the decoder works on the
-    matcher's decoder_base(), errors over the k - fillers message positions."""
+    matcher's decoder_base(), errors over the k - fillers message positions.
+
+    fixed: None, or (llr_scale, llr_max, msg_max): the int8 fixed-point decoder
+    QCFixedMSDecoder with these parameters instead (`dtype` is not used; the
+    channel LLRs stay fp64 and the decoder quantises them).  The three values
+    enter the log's run key, as "fixed", only when given."""
     import torch
-    from ..ldpc.decoder import QCLayeredMSDecoder
+    from ..ldpc.decoder import QCFixedMSDecoder, QCLayeredMSDecoder
     from ..ldpc.encoder import QCLDPCEncoder
     base = np.asarray(base, dtype=np.int64)
+    more = {}
+    if fixed is not None:
+        fixed = (float(fixed[0]), int(fixed[1]), int(fixed[2]))
+        more["fixed"] = list(fixed)
+
+    def make_decoder(b):
+        if fixed is None:
+            return QCLayeredMSDecoder(b, Z, max_iter=max_iter, normalization=normalization, early_stop=True, dtype=dtype)
+        return QCFixedMSDecoder(b, Z, max_iter=max_iter, normalization=normalization, early_stop=True,
+                                llr_scale=fixed[0], llr_max=fixed[1], msg_max=fixed[2])
+
+    def dtype_name(dec):
+        return "int8" if fixed is not None else np.dtype(dec.dtype).name
     if rate_match is not None:
         from ..ldpc.ratematch import QCRateMatcher
         rm = QCRateMatcher(base, Z, **rate_match) if isinstance(rate_match, dict) else QCRateMatcher(base, Z, *rate_match)
-        dec = QCLayeredMSDecoder(rm.decoder_base(), Z, max_iter=max_iter, normalization=normalization,
-                                 early_stop=True, dtype=dtype)
+        dec = make_decoder(rm.decoder_base())
         k = rm.k - rm.fillers
         enc = QCLDPCEncoder(base, Z) if random_codewords else None
         mc = MonteCarlo(ldpc_round_fn(dec, seed=seed, encoder=enc, rate_matcher=rm), info_bits=k, batch=batch,
                         group=group, device=torch.device("cuda", torch.cuda.current_device()))
         log = _log(log_path, mc, code="qcldpc", n=rm.n, k=k, Z=int(Z), max_iter=max_iter, norm=float(normalization),
-                   dtype=np.dtype(dec.dtype).name, random=random_codewords, frames=num_frames, max_errors=max_errors,
+                   dtype=dtype_name(dec), random=random_codewords, frames=num_frames, max_errors=max_errors,
                    seed=seed, base=_digest(base + 1), rm=[rm.E, rm.punctured, rm.fillers, rm.ncb, rm.start],
-                   filler_llr=rm.filler_llr, n_dec=rm.n_dec)
+                   filler_llr=rm.filler_llr, n_dec=rm.n_dec, **more)
         pts = mc.run(snr_db_range, num_frames, max_errors, log=log)
         return np.array([p.ber for p in pts]), np.array([p.fer for p in pts]), pts
-    dec = QCLayeredMSDecoder(base, Z, max_iter=max_iter, normalization=normalization, early_stop=True, dtype=dtype)
+    dec = make_decoder(base)
     k = dec.n - dec.m
     enc = QCLDPCEncoder(base, Z) if random_codewords else None
     mc = MonteCarlo(ldpc_round_fn(dec, seed=seed, info_bits=k, encoder=enc), info_bits=k, batch=batch, group=group,
                     device=torch.device("cuda", torch.cuda.current_device()))
     log = _log(log_path, mc, code="qcldpc", n=dec.n, k=k, Z=int(Z), max_iter=max_iter, norm=float(normalization),
-               dtype=np.dtype(dec.dtype).name, random=random_codewords, frames=num_frames, max_errors=max_errors,
-               seed=seed, base=_digest(base + 1))
+               dtype=dtype_name(dec), random=random_codewords, frames=num_frames, max_errors=max_errors,
+               seed=seed, base=_digest(base + 1), **more)
     pts = mc.run(snr_db_range, num_frames, max_errors, log=log)
     return np.array([p.ber for p in pts]), np.array([p.fer for p in pts]), pts
 
@@ -204,6 +222,9 @@ def main(argv=None):
                          "of each frame are transmitted")
     ap.add_argument("--dtype", choices=["float64", "float32"], default="float64",
                     help="--code qcldpc: the decoder's state and arithmetic")
+    ap.add_argument("--fixed", default=None,
+                    help="--code qcldpc: scale,llr_max,msg_max, the int8 fixed-point decoder (ldpc.QCFixedMSDecoder) "
+                         "instead of the floating one; --dtype is then not used")
     ap.add_argument("--norm", type=float, default=0.75, help="--code qcldpc: min-sum normalisation")
     ap.add_argument("--seed", type=int, default=0, help="--code qcldpc: seed of the frame source")
     ap.add_argument("--cpu-stub", action="store_true",
@@ -241,6 +262,11 @@ def main(argv=None):
             if len(rm) not in (3, 4, 5):
                 ap.error("--rm takes E,punctured,fillers[,ncb[,start]]")
         more = {} if rm is None else {"rate_match": rm}
+        if a.fixed is not None:
+            fx = a.fixed.split(",")
+            if len(fx) != 3:
+                ap.error("--fixed takes scale,llr_max,msg_max")
+            more["fixed"] = (float(fx[0]), int(fx[1]), int(fx[2]))
         ber, fer, pts = simulate_qc_ldpc(snr, a.frames, a.max_errors, base, q[2], max_iter=a.max_iter,
                                          normalization=a.norm, dtype=np.dtype(a.dtype).type, batch=a.batch,
                                          seed=a.seed, random_codewords=a.ldpc_codewords == "random", log_path=a.log,

@@ -248,6 +248,14 @@ def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None)
     return fn
 
 
+def _plan_decode(decoder, llr, out, its):
+    """decoder.plan.decode(llr, out, its); a fixed-point decoder (ldpc.QCFixedMSDecoder) quantises the
+    floating LLRs on the device first: the channel and the recovery stay floating."""
+    if getattr(decoder.plan, "fixed", False):
+        llr = decoder.quantize(llr)
+    decoder.plan.decode(llr, out, its)
+
+
 def _rate_matched_round_fn(decoder, seed, encoder, rm):
     """ldpc_round_fn's rate-matched chain; see there."""
     import torch
@@ -287,7 +295,7 @@ def _rate_matched_round_fn(decoder, seed, encoder, rm):
             AWGNChannel(snr_db).llr_batch_device(tx, E, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=rx)
             ref = msg
         rm.recover(rx, out=llr)
-        decoder.plan.decode(llr, out, its)
+        _plan_decode(decoder, llr, out, its)
         _native.count_errors(ref, out, kf, counts)
         return counts.cpu().numpy()
 
@@ -296,7 +304,8 @@ def _rate_matched_round_fn(decoder, seed, encoder, rm):
 
 def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encoder=None, rate_matcher=None):
     """Round function for BPDecoder / MSDecoder / LayeredMSDecoder (any decoder
-    with `.plan`, `.n` and `.m`).
+    with `.plan`, `.n` and `.m`).  A QCFixedMSDecoder takes the same chain: the
+    channel LLRs (and the recovery) stay fp64 and the decoder quantises them.
 
     encoder None: the all-zero codeword (BP and min-sum are codeword-symmetric);
     errors over the first `info_bits` positions, like ber_simulation.py:265-269
@@ -337,13 +346,13 @@ def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encod
         counts = torch.zeros(3, dtype=torch.int64, device="cuda")
         if encoder is None:
             AWGNChannel(snr_db).llr_batch_device(None, n, nframes, seed=s, frame_offset=offset, out=llr)
-            decoder.plan.decode(llr, out, its)
+            _plan_decode(decoder, llr, out, its)
             _native.count_errors(zero, out, k, counts)
         else:
             _native.random_bits(s, offset, msg)
             encoder.encode_batch_device(msg, out=cw)
             AWGNChannel(snr_db).llr_batch_device(cw, n, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=llr)
-            decoder.plan.decode(llr, out, its)
+            _plan_decode(decoder, llr, out, its)
             _native.count_errors(msg, out.index_select(1, info).contiguous(), k, counts)
         return counts.cpu().numpy()
 

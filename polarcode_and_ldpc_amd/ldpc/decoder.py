@@ -5,7 +5,8 @@ src/ldpc/decoder.py (BPDecoder :11-205, MSDecoder :208-355), plus
 `decode_batch` for host or device batches.  No CPU path.
 LayeredMSDecoder (ldpc_layered.hip) is a build-defined extension: the serial
 schedule with posterior LLR output; QCLayeredMSDecoder (ldpc_qc_layered.hip) is
-the same decoder for a quasi-cyclic code given by its base matrix.
+the same decoder for a quasi-cyclic code given by its base matrix, and
+QCFixedMSDecoder (ldpc_qc_fixed.hip) its int8 fixed-point counterpart.
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ import torch
 from .. import _native
 from .matrix import dense_to_csr, layer_schedule, qc_block_layers, qc_expand
 
-_TORCH = {np.float64: torch.float64, np.float32: torch.float32}
+_TORCH = {np.float64: torch.float64, np.float32: torch.float32, np.int8: torch.int8}
 
 
 class _LdpcBase:
@@ -298,3 +299,112 @@ class QCLayeredMSDecoder(LayeredMSDecoder):
     def __repr__(self) -> str:
         return (f"QCLayeredMSDecoder(n={self.n}, m={self.m}, Z={self.Z}, max_iter={self.max_iter}, "
                 f"norm={self.normalization}" + (", dtype=float32)" if self.dtype == np.float32 else ")"))
+
+
+def quantize_host(llr, scale: float, llr_max: int) -> np.ndarray:
+    """The LLR quantiser of the fixed-point decoder on the host (include/polarldpc.h, pl_llr_quantize):
+    clamp(rint(double(llr) * scale), -llr_max, llr_max) as int8, rint half to even, NaN -> 0, +-inf ->
+    +-llr_max.  float64 and float32 (widened exactly) as they are; any other dtype through float64."""
+    a = np.asarray(llr)
+    if a.dtype not in (np.float64, np.float32):
+        a = a.astype(np.float64)
+    assert np.isfinite(scale) and scale > 0 and 1 <= llr_max <= 127
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = np.rint(a.astype(np.float64) * np.float64(scale))
+    return np.clip(np.where(np.isnan(x), 0.0, x), -float(llr_max), float(llr_max)).astype(np.int8)
+
+
+class QCFixedMSDecoder(LayeredMSDecoder):
+    """int8 fixed-point layered normalised min-sum for a quasi-cyclic code given by
+    its base matrix (ldpc_qc_fixed.hip).  `base`, `Z` and `layer_order` as
+    QCLayeredMSDecoder's.  The definition -- integer arithmetic with three
+    saturation bounds, exactly reproducible -- is printed in include/polarldpc.h at
+    pl_ldpc_qc_fixed_plan_create: posteriors saturate at 127, channel LLRs at
+    `llr_max`, check-to-variable messages at `msg_max`, and the normalisation is
+    `normalization` = norm16 / 16 with norm16 an integer in 1 .. 16 (ValueError
+    otherwise).
+
+    decode / decode_batch take int8 LLRs (NumPy arrays, or CUDA tensors with any row
+    pitch) as they are, and floating LLRs through the quantiser
+    L = clamp(rint(llr * llr_scale), -llr_max, llr_max): CUDA tensors through the
+    device kernel (fp64 and fp32 as they are, other floating types through fp32),
+    NumPy arrays through quantize_host and one upload.  return_llr gives the final
+    int8 posteriors."""
+
+    _elem = np.int8
+
+    def __init__(self, base: np.ndarray, Z: int, max_iter: int = 50, normalization: float = 0.75,
+                 early_stop: bool = True, layer_order=None, llr_scale: float = 4.0, llr_max: int = 31,
+                 msg_max: int = 31):
+        n16 = float(normalization) * 16.0
+        if n16 != int(n16) or not 1 <= int(n16) <= 16:
+            raise ValueError("QCFixedMSDecoder: normalization * 16 must be an integer in 1 .. 16, not %r" % (n16,))
+        if not (np.isfinite(llr_scale) and llr_scale > 0):
+            raise ValueError("QCFixedMSDecoder: llr_scale must be finite and > 0, not %r" % (llr_scale,))
+        self._algo = _native.PL_LDPC_LMS
+        self.base = np.array(base, dtype=np.int64)
+        assert self.base.ndim == 2, "base must be [mb, nb]"
+        self.Z = int(Z)
+        self.mb, self.nb = self.base.shape
+        self.m, self.n = self.mb * self.Z, self.nb * self.Z
+        self.max_iter = max_iter
+        self.early_stop = early_stop
+        self.normalization = normalization
+        self.norm16 = int(n16)
+        self.llr_scale, self.llr_max, self.msg_max = float(llr_scale), int(llr_max), int(msg_max)
+        self.layer_order = None if layer_order is None else [int(i) for i in layer_order]
+        self.check_degrees = np.repeat((self.base >= 0).sum(axis=1), self.Z)
+        self.var_neighbors = None
+        self._plan = None
+        self._H = None
+
+    H = QCLayeredMSDecoder.H
+    layers = QCLayeredMSDecoder.layers
+
+    @property
+    def plan(self):
+        if self._plan is None:
+            self._plan = _native.qc_fixed_ldpc_plan(self.base, self.Z, self.layer_order, self.max_iter,
+                                                    self.early_stop, self.norm16, self.llr_max, self.msg_max)
+        return self._plan
+
+    def quantize_host(self, llr) -> np.ndarray:
+        return quantize_host(llr, self.llr_scale, self.llr_max)
+
+    def quantize(self, llr: "torch.Tensor", out: Optional[torch.Tensor] = None) -> "torch.Tensor":
+        """A floating CUDA tensor [B, >= n] (unit inner stride, any row pitch) -> int8 [B, n] on the device
+        (pl_llr_quantize); `out`: an int8 [B, n] device tensor or view to write into."""
+        if not llr.dtype.is_floating_point:
+            raise TypeError("QCFixedMSDecoder: LLRs must be int8 or floating, not %s" % (llr.dtype,))
+        if llr.dtype not in (torch.float64, torch.float32):
+            llr = llr.to(torch.float32)  # exact for the narrower floating types
+        if llr.stride(1) != 1:
+            llr = llr.contiguous()
+        if out is None:
+            out = torch.empty((llr.shape[0], self.n), dtype=torch.int8, device=llr.device)
+        _native.llr_quantize(llr, self.llr_scale, self.llr_max, out)
+        return out
+
+    def _device_llr(self, llr):
+        if llr.dtype != torch.int8:
+            return self.quantize(llr)
+        return llr if llr.stride(1) == 1 else llr.contiguous()
+
+    def _host_llr(self, llr):
+        a = np.asarray(llr)
+        if a.dtype == np.int8:
+            return a
+        if not np.issubdtype(a.dtype, np.floating):
+            raise TypeError("QCFixedMSDecoder: LLRs must be int8 or floating, not %s" % (a.dtype,))
+        return self.quantize_host(a)
+
+    def decode(self, llr: np.ndarray, return_iterations: bool = False):
+        assert len(llr) == self.n, f"LLR length must be {self.n}"
+        bits, its = self.decode_batch(np.asarray(llr)[None, :], return_iterations=True)
+        if return_iterations:
+            return bits[0], int(its[0])
+        return bits[0]
+
+    def __repr__(self) -> str:
+        return (f"QCFixedMSDecoder(n={self.n}, m={self.m}, Z={self.Z}, max_iter={self.max_iter}, "
+                f"norm={self.norm16}/16, llr_scale={self.llr_scale}, llr_max={self.llr_max}, msg_max={self.msg_max})")

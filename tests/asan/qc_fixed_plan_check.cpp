@@ -1,0 +1,137 @@
+// The fixed-point quasi-cyclic plan builder (csrc/ldpc_plan.cpp,
+// qc_fixed_plan_build) under AddressSanitizer + UBSan, compiled together with
+// this file alone: no HIP, no library.  Every refusal must come back with its
+// code and a message, in the documented order, before a table is written; the
+// state layout is the documented one; the layer stream is qc_plan_build's.
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "../../include/polarldpc.h"
+#include "../../polarcode_and_ldpc_amd/csrc/ldpc_plan.hpp"
+
+static int failures = 0;
+#define EXPECT(cond)                                                       \
+    do {                                                                   \
+        if (!(cond)) {                                                     \
+            std::fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+            ++failures;                                                    \
+        }                                                                  \
+    } while (0)
+
+// column j of an mb x nb base gets dv blocks in rows (j + k) mod mb, shift (3 j + 5 k) mod z
+static std::vector<int32_t> base(int mb, int nb, int z, int dv) {
+    std::vector<int32_t> s((size_t)mb * nb, -1);
+    for (int j = 0; j < nb; ++j)
+        for (int k = 0; k < dv; ++k) s[(size_t)((j + k) % mb) * nb + j] = (3 * j + 5 * k) % z;
+    return s;
+}
+
+struct Params { int norm16 = 12, llr_max = 31, msg_max = 31; };
+
+static pl::PlanStatus build(int mb, int nb, int z, const std::vector<int32_t>& s, const int32_t* order, int max_iter,
+                            pl::QcFixedHostPlan* hp, bool global = false, Params p = Params()) {
+    pl::LdpcPlanOptions opt;
+    opt.lms_global = global;
+    return pl::qc_fixed_plan_build(mb, nb, z, s.data(), order, max_iter, 1, p.norm16, p.llr_max, p.msg_max, opt, hp);
+}
+
+static int64_t align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
+
+int main() {
+    pl::QcFixedHostPlan hp;
+    pl::QcHostPlan fl;
+    // valid plans: each mapping, each register cap, both state homes; maxdc = ceil(nb dv / mb) here
+    struct Shape { int mb, nb, z, dv, dcap, mw, subwave, fpw, global; };
+    const Shape shapes[] = {{4, 8, 1, 3, 8, 1, 1, 64, 0},    {4, 8, 7, 3, 8, 1, 1, 9, 0},    {4, 8, 27, 3, 8, 1, 1, 2, 0},
+                            {4, 8, 64, 3, 8, 1, 1, 1, 0},    {4, 8, 96, 3, 8, 1, 0, 1, 0},   {3, 16, 7, 3, 16, 2, 1, 9, 0},
+                            {3, 30, 7, 3, 32, 2, 1, 9, 0},   {3, 40, 7, 3, 0, 3, 1, 9, 0},   {32, 64, 160, 3, 8, 1, 0, 1, 0},
+                            {32, 64, 1024, 3, 8, 1, 0, 1, 1}, {4, 8, 1024, 3, 8, 1, 0, 1, 0}, {1, 2047, 1, 1, 0, 65, 1, 64, 0},
+                            {2, 300, 64, 2, 0, 11, 1, 1, 0}};
+    for (const Shape& sh : shapes) {
+        const std::vector<int32_t> s = base(sh.mb, sh.nb, sh.z, sh.dv);
+        const pl::PlanStatus st = build(sh.mb, sh.nb, sh.z, s, nullptr, 20, &hp);
+        EXPECT(st.code == PL_OK);
+        const pl::QcFixedGeom& g = hp.geom;
+        EXPECT(g.dcap == sh.dcap && g.mw == sh.mw && g.subwave == sh.subwave && g.fpw == sh.fpw &&
+               g.use_global == sh.global);
+        EXPECT(g.n == sh.nb * sh.z && g.m == sh.mb * sh.z && pl::qc_fixed_kernel_code(g) == (sh.global ? 16 : 15));
+        EXPECT(g.norm16 == 12 && g.llr_max == 31 && g.msg_max == 31);
+        // the documented layout: [m][mw] u32 check words, then P[n] int8
+        EXPECT(g.off_p == (int64_t)4 * g.m * g.mw && g.state_bytes == align16(g.off_p + g.n));
+        EXPECT(g.maxdc > 32 || g.state_bytes == align16((int64_t)g.n + (g.maxdc <= 14 ? 4 : 8) * (int64_t)g.m));
+        EXPECT(g.use_global || g.lds_bytes <= 160 * 1024);
+        EXPECT(g.use_global ? g.lds_bytes == (g.subwave ? 0 : pl::kLdpcVoteBytes)
+                            : g.lds_bytes == (g.subwave ? (int)(g.state_bytes * g.fpw * g.fpb)
+                                                        : (int)g.state_bytes + pl::kLdpcVoteBytes));
+        EXPECT(g.threads == (g.subwave ? 64 * g.fpb : (sh.z + 63) / 64 * 64));
+        // the stream is the floating-point plan's, word for word
+        pl::LdpcPlanOptions opt;
+        EXPECT(pl::qc_plan_build(sh.mb, sh.nb, sh.z, s.data(), nullptr, 20, 1, 0.75, opt, &fl).code == PL_OK);
+        EXPECT(hp.tables == fl.tables && hp.tables.size() == 2 * (size_t)sh.mb + 2 * (size_t)sh.nb * sh.dv);
+        EXPECT(g.dcap == fl.geom.dcap && g.subwave == fl.geom.subwave && g.fpw == fl.geom.fpw);
+        EXPECT(g.state_bytes < fl.geom.state_bytes);
+        EXPECT(build(sh.mb, sh.nb, sh.z, s, nullptr, 20, &hp, true).code == PL_OK && hp.geom.use_global == 1 &&
+               pl::qc_fixed_kernel_code(hp.geom) == 16);
+    }
+    const std::vector<int32_t> s = base(4, 8, 7, 3);
+    const int32_t order[] = {2, 0, 3, 1};
+    EXPECT(build(4, 8, 7, s, order, 20, &hp).code == PL_OK && hp.tables[0] == 2);
+    // the bounds of the three parameters are inside
+    for (const Params& p : {Params{1, 1, 1}, Params{16, 127, 127}})
+        EXPECT(build(4, 8, 7, s, nullptr, 20, &hp, false, p).code == PL_OK && hp.geom.norm16 == p.norm16 &&
+               hp.geom.llr_max == p.llr_max && hp.geom.msg_max == p.msg_max);
+
+    // refusals
+    auto refused = [&](int code, const pl::PlanStatus& st, const char* word = "") {
+        return st.code == code && !st.msg.empty() && st.msg.find(word) != std::string::npos;
+    };
+    hp.tables.assign(3, 77);  // no refusal touches the tables
+    EXPECT(refused(PL_EINVAL, build(0, 8, 7, s, nullptr, 20, &hp)));
+    EXPECT(refused(PL_EINVAL, build(4, 0, 7, s, nullptr, 20, &hp)));
+    EXPECT(refused(PL_EINVAL, build(4, 8, 0, s, nullptr, 20, &hp)));
+    EXPECT(refused(PL_EINVAL, pl::qc_fixed_plan_build(4, 8, 7, nullptr, nullptr, 20, 1, 12, 31, 31, {}, &hp)));
+    const std::vector<int32_t> two = {0, 0};
+    EXPECT(refused(PL_EINVAL, build(1, 2, 1 << 30, two, nullptr, 20, &hp)));  // nb z = 2^31, before any shift is read
+    EXPECT(refused(PL_EINVAL, build(2, 1, 1 << 30, two, nullptr, 20, &hp)));
+    EXPECT(refused(PL_EINVAL, build(4, 8, 7, s, nullptr, -1, &hp), "max_iter"));
+    for (int bad : {-2, 7, INT32_MAX, INT32_MIN}) {
+        std::vector<int32_t> b = s;
+        b[31] = bad;
+        EXPECT(refused(PL_EINVAL, build(4, 8, 7, b, nullptr, 20, &hp), "shift"));
+    }
+    for (const std::vector<int32_t>& o : {std::vector<int32_t>{0, 1, 2, 2}, {0, 1, 2, 4}, {-1, 0, 1, 2}, {0, 1, 2, INT32_MAX}})
+        EXPECT(refused(PL_EINVAL, build(4, 8, 7, s, o.data(), 20, &hp), "layer_order"));
+    for (int bad : {0, 17, -1, INT32_MAX, INT32_MIN}) {
+        EXPECT(refused(PL_EINVAL, build(4, 8, 7, s, nullptr, 20, &hp, false, {bad, 31, 31}), "norm16"));
+        EXPECT(refused(PL_EINVAL, build(4, 8, 7, s, nullptr, 20, &hp, false, {bad, 0, 0}), "norm16"));  // the first one
+    }
+    for (int bad : {0, 128, -1, INT32_MAX, INT32_MIN}) {
+        EXPECT(refused(PL_EINVAL, build(4, 8, 7, s, nullptr, 20, &hp, false, {12, bad, 31}), "llr_max"));
+        EXPECT(refused(PL_EINVAL, build(4, 8, 7, s, nullptr, 20, &hp, false, {12, bad, 0}), "llr_max"));
+        EXPECT(refused(PL_EINVAL, build(4, 8, 7, s, nullptr, 20, &hp, false, {12, 31, bad}), "msg_max"));
+    }
+    // the order: the floating-point plan's checks, the three parameters behind layer_order, then PL_EUNSUPPORTED
+    const int32_t bad_order[] = {0, 1, 2, 2};
+    EXPECT(refused(PL_EINVAL, build(4, 8, 7, s, bad_order, 20, &hp, false, {0, 31, 31}), "layer_order"));
+    EXPECT(refused(PL_EINVAL, build(4, 8, 7, s, nullptr, -1, &hp, false, {0, 31, 31}), "max_iter"));
+    std::vector<int32_t> one = s;
+    for (int j = 0; j < 8; ++j) one[j] = j == 3 ? 5 : -1;
+    EXPECT(refused(PL_EUNSUPPORTED, build(4, 8, 7, one, nullptr, 20, &hp), "degree-1"));
+    EXPECT(refused(PL_EINVAL, build(4, 8, 7, one, nullptr, 20, &hp, false, {12, 31, 128}), "msg_max"));  // EINVAL first
+    EXPECT(hp.tables == std::vector<int32_t>(3, 77));
+    EXPECT(build(4, 8, 7, one, nullptr, 0, &hp).code == PL_OK);
+    std::vector<int32_t> none = s;
+    for (int j = 0; j < 8; ++j) none[8 + j] = -1;  // an empty block row is fine
+    EXPECT(build(4, 8, 7, none, nullptr, 20, &hp).code == PL_OK && hp.tables.size() == 2 * 4 + 2 * 18);
+    EXPECT(refused(PL_EUNSUPPORTED, build(1, 2048, 1, std::vector<int32_t>(2048, 0), nullptr, 20, &hp), "2048"));
+    EXPECT(refused(PL_EUNSUPPORTED, build(1, 2, 1025, two, nullptr, 20, &hp), "1024"));
+    EXPECT(refused(PL_EINVAL, build(1, 2, 1025, two, nullptr, 20, &hp, false, {17, 31, 31}), "norm16"));
+
+    if (failures) {
+        std::fprintf(stderr, "%d check(s) failed\n", failures);
+        return 1;
+    }
+    std::puts("all checks passed");
+    return 0;
+}

@@ -1,6 +1,7 @@
 """LDPC decode kernel timing (diagnostic): HIP events around repeated launches.
 
-usage: python tools/ldpc_bench.py [--batch 65536] [--algo bp,ms,lms,qclms,qclms32] [--n 504] [--seed 3]
+usage: python tools/ldpc_bench.py [--batch 65536] [--algo bp,ms,lms,qclms,qclms32,qclms8] [--n 504] [--seed 3]
+                                  [--fixed 4,31,31]
                                   [--qc mb,nb,Z,dv,seed] [--qc-encodable]
                                   [--random-codewords] [--max-iter 20] [--no-early-stop]
                                   [--snr 3.0] [--valid] [--norm 0.75] [--reps 5] [--rounds 3]
@@ -17,6 +18,9 @@ frames must be equal (asserted).  `qclms32` is QCLayeredMSDecoder(dtype=float32)
 on the same device frames, cast once to fp32 outside the timed region; it is
 another decoder (every operation in binary32), so its results are reported, not
 compared: `frames_differ_from_qclms` counts the frames whose bits differ.
+`qclms8` is QCFixedMSDecoder (int8 fixed point, --fixed scale,llr_max,msg_max) on the
+same device frames, quantised once by the decoder's own kernel outside the timed
+region; reported like qclms32, with `frames_differ_from_qclms32` when both run.
 --qc-encodable: the code qc_encodable_base(mb, nb, Z, dv, seed) instead, whose parity
 part QCLDPCEncoder can encode from; without it --qc means what it always meant.
 --random-codewords (needs --qc-encodable): the frames carry random messages encoded on
@@ -33,7 +37,7 @@ import numpy as np, torch
 from polarcode_and_ldpc_amd.channel import AWGNChannel
 from polarcode_and_ldpc_amd import _native
 from polarcode_and_ldpc_amd.ldpc import (BPDecoder, MSDecoder, LayeredMSDecoder, LDPCEncoder, QCLDPCEncoder,
-                                         QCLayeredMSDecoder, qc_block_layers, qc_encodable_base, qc_random_base,
+                                         QCFixedMSDecoder, QCLayeredMSDecoder, qc_block_layers, qc_encodable_base, qc_random_base,
                                          qc_to_csr, regular_construction)
 
 ap = argparse.ArgumentParser()
@@ -50,6 +54,7 @@ ap.add_argument("--qc", default="", help="mb,nb,Z,dv,seed: a qc_random_base code
 ap.add_argument("--qc-encodable", action="store_true", help="--qc builds qc_encodable_base(mb, nb, Z, dv, seed)")
 ap.add_argument("--random-codewords", action="store_true",
                 help="--qc-encodable: random codewords from QCLDPCEncoder instead of the all-zero one")
+ap.add_argument("--fixed", default="4,31,31", help="qclms8: llr_scale,llr_max,msg_max")
 ap.add_argument("--reps", type=int, default=5, help="launches per timed round")
 ap.add_argument("--rounds", type=int, default=3)
 a = ap.parse_args()
@@ -106,10 +111,14 @@ def make(spec):
             return QCLayeredMSDecoder(qc, Z, max_iter=mi, normalization=a.norm, early_stop=es)
         if name == "qclms32":
             return QCLayeredMSDecoder(qc, Z, max_iter=mi, normalization=a.norm, early_stop=es, dtype=np.float32)
+        if name == "qclms8":
+            fs, fl, fm = a.fixed.split(",")
+            return QCFixedMSDecoder(qc, Z, max_iter=mi, normalization=a.norm, early_stop=es, llr_scale=float(fs),
+                                    llr_max=int(fl), msg_max=int(fm))
         if name == "lms":
             return GenericOnQc(mi)
-        raise SystemExit("--qc takes --algo lms, qclms and qclms32 only, not %r" % spec)
-    if name in ("qclms", "qclms32"):
+        raise SystemExit("--qc takes --algo lms, qclms, qclms32 and qclms8 only, not %r" % spec)
+    if name in ("qclms", "qclms32", "qclms8"):
         raise SystemExit("--algo %s needs --qc mb,nb,Z,dv,seed" % name)
     if name == "bp":
         return BPDecoder(H, max_iter=mi, early_stop=es)
@@ -129,9 +138,13 @@ llr = AWGNChannel(a.snr).llr_batch_device(cw, n, B, seed=4242)
 llr32 = llr.to(torch.float32) if any(s.partition(":")[0] == "qclms32" for s in specs) else None
 
 
+llr8 = {s: d.quantize(llr) for s, d in zip(specs, decs) if s.partition(":")[0] == "qclms8"}
+
+
 def frames_of(spec):
-    """The timed frames in the type the decoder reads: fp32 for qclms32 (cast above, once), else fp64."""
-    return llr32 if spec.partition(":")[0] == "qclms32" else llr
+    """The timed frames in the type the decoder reads: fp32 for qclms32 (cast above, once), int8 for
+    qclms8 (quantised above, once), else fp64."""
+    return llr8[spec] if spec in llr8 else llr32 if spec.partition(":")[0] == "qclms32" else llr
 
 
 out = torch.empty((B, n), dtype=torch.uint8, device="cuda")
@@ -155,6 +168,9 @@ if qc is not None:  # the two decoders are one definition: equal on the timed fr
     if "qclms" in names and "qclms32" in names:
         (b0, _), (b1, _) = results[names["qclms"]], results[names["qclms32"]]
         stats[specs.index(names["qclms32"])]["frames_differ_from_qclms"] = int((b0 != b1).any(dim=1).sum())
+    if "qclms32" in names and "qclms8" in names:
+        (b0, _), (b1, _) = results[names["qclms32"]], results[names["qclms8"]]
+        stats[specs.index(names["qclms8"])]["frames_differ_from_qclms32"] = int((b0 != b1).any(dim=1).sum())
 times = [[] for _ in decs]
 for _ in range(a.rounds):
     for i, d in enumerate(decs):  # alternated, so drift hits every decoder alike
@@ -173,6 +189,6 @@ for s, d, t, st in zip(specs, decs, times, stats):
                       "mean_iter": st["mean_iter"], "frame_errors": st["frame_errors"],
                       **({"codewords": "random"} if a.random_codewords else {}),
                       "plan_kernel": int(d.plan.info.reserved), "lds_bytes": int(d.plan.info.lds_bytes),
-                      **({"frames_differ_from_qclms": st["frames_differ_from_qclms"]}
-                         if "frames_differ_from_qclms" in st else {}),
+                      **{k: st[k] for k in ("frames_differ_from_qclms", "frames_differ_from_qclms32") if k in st},
+                      "frames_per_block": int(d.plan.info.frames_per_block),
                       "kernel": os.environ.get("PL_LDPC_KERNEL", "default")}))
