@@ -79,6 +79,18 @@ namespace {
 #ifndef PL_LIST_U
 #define PL_LIST_U 8  // list instances: workspace parent pairs in flight per g-chain batch
 #endif
+#ifndef PL_BUF_ADDR
+#define PL_BUF_ADDR -1  // 1 / 0: workspace and channel accesses through buffer descriptors (-1: TG::BUF's rule)
+#endif
+#ifndef PL_LIST_U_TOP
+#define PL_LIST_U_TOP -1  // list instances: the same for the parents of depths F, F + 1 (-1: TG::U_TOP's rule)
+#endif
+#ifndef PL_FT_CH
+#define PL_FT_CH -1  // de-duplicated fused top at LCAP = 8: pairs per lane per chunk (-1: TG::FT_CH's rule)
+#endif
+#ifndef PL_FT_PF_IN
+#define PL_FT_PF_IN -1  // 1 / 0: the fused top's chunk prefetch inside the element loop at LCAP = 8 (-1: TG::WIDE)
+#endif
 #ifndef PL_FT_UNR32
 #define PL_FT_UNR32 2  // L = 32: the fused top's element-loop unroll
 #endif
@@ -311,6 +323,90 @@ struct TG {
         return STAGE && LCAP >= (1 << (F - D0)) / 2 && (1 << (n - F)) * ((1 << (F - D0)) / 2) >= LCAP;
     }
     static PL_DEV int pl(int s, int f) { return SHADOW ? s * FPW + f : f * LCAP + s; }
+    // Workspace and channel accesses through buffer descriptors (Span) instead
+    // of flat 64-bit lane addresses; per instance, flat where it measured slower
+    // (every list instance; SC measured 2 % slower with it, profiles/r07_a/ab_stage1_all.log,
+    // and runs the flat forms of Span / Chan: the same accesses as before, not the same code)
+    static constexpr bool BUF = PL_BUF_ADDR >= 0 ? PL_BUF_ADDR != 0 : LCAP != 1;
+    // The registers that frees (N = 1024 L = 8: 128 VGPRs + 56 spilled bytes ->
+    // 123, nothing spilled) spent on loads in flight, where it was measured --
+    // the headline instance: 16 parent pairs per g-chain batch at the parents
+    // of depths F, F + 1, two pairs per lane per fused-top chunk and its
+    // prefetch inside the element loop.  Each lost to spills with flat
+    // addresses; together -2.9 % (profiles/r07_a/ab_stage2.log)
+    static constexpr bool WIDE = BUF && n == 10 && LCAP == 8 && F == 3 && DL == 7;
+    static constexpr int U_TOP = PL_LIST_U_TOP > 0 ? PL_LIST_U_TOP : (WIDE ? 16 : PL_LIST_U);
+    static constexpr int FT_CH = LCAP != 8 ? 1 : (PL_FT_CH > 0 ? PL_FT_CH : (WIDE ? 2 : 1));
+    static constexpr bool FT_PF_IN = LCAP >= 16 || (LCAP == 8 && (PL_FT_PF_IN >= 0 ? PL_FT_PF_IN != 0 : WIDE));
+    static_assert(!STAGE || 2 * FPW * GS >= 1024 * FT_CH, "metric/row scratch holds a staging chunk");
+    static_assert(WS < (1LL << 31), "a wave's workspace slice is addressed with 32-bit offsets");
+};
+
+// ---- scalar-base addressing (TG::BUF) --------------------------------------
+// Every workspace and channel address is a wave-uniform base + a wave-uniform
+// term (compile-time offset, loop counter) + a small lane term (plane * 16 or
+// * 4).  As flat pointers each access holds a 64-bit address in a VGPR pair
+// and pays 64-bit VALU adds; through a buffer descriptor the base lives in 4
+// SGPRs, the lane term in one 32-bit VGPR and the uniform term in an SGPR.
+// A Span is such a range: flat (BUF = false) it is the plain pointer sum.  The
+// descriptor is sized to the range, so an addressing bug reads zeros or drops
+// a store instead of reaching another wave's memory (not relied on: dead
+// lanes stay clamped to frame batch - 1).
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+constexpr int BUF_NT = 2;  // cache-policy bit of a streaming (nt) buffer access
+
+template <bool BUF>
+struct Span {
+    unsigned char* p;
+    __amdgpu_buffer_rsrc_t r;
+    // base and bytes wave-uniform
+    PL_DEV Span(const void* base, uint32_t bytes)
+        : p(static_cast<unsigned char*>(const_cast<void*>(base))),
+          r(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)(BUF ? bytes : 0u), 0x00020000)) {}
+    // lo: the lane's byte offset (VGPR); uo: the wave-uniform byte offset
+    template <bool NT = false>
+    PL_DEV double2 ld_pair(uint32_t lo, uint32_t uo) const {
+        if constexpr (BUF) {
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)lo, (int)uo, NT ? BUF_NT : 0);
+            return make_double2(__hiloint2double((int)v.y, (int)v.x), __hiloint2double((int)v.w, (int)v.z));
+        } else {
+            const double2* a = reinterpret_cast<const double2*>(p + lo + uo);
+            if constexpr (NT) return make_double2(__builtin_nontemporal_load(&a->x), __builtin_nontemporal_load(&a->y));
+            else return *a;
+        }
+    }
+    template <bool NT = false>
+    PL_DEV void st_pair(uint32_t lo, uint32_t uo, double x, double y) const {
+        if constexpr (BUF) {
+            const u32x4 v = {(unsigned)__double2loint(x), (unsigned)__double2hiint(x), (unsigned)__double2loint(y),
+                             (unsigned)__double2hiint(y)};
+            // The uniform term goes into the VGPR offset, not an SGPR.  A 16-byte
+            // store reads its data registers over several cycles and a VALU
+            // write to them right behind it needs wait states; the compiler
+            // inserts them for a buffer store only when its scalar offset is
+            // not a register.  With an SGPR offset the lanes 8..15 of each row
+            // of 16 stored what the next instruction wrote (seen as a few
+            // percent of wrong frames at -2 dB, odd frame slots only).  The
+            // scalar-offset argument below must stay the literal 0.
+            __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)(lo + uo), 0, NT ? BUF_NT : 0);
+        } else {
+            double2* a = reinterpret_cast<double2*>(p + lo + uo);
+            if constexpr (NT) {
+                __builtin_nontemporal_store(x, &a->x);
+                __builtin_nontemporal_store(y, &a->y);
+            } else {
+                *a = make_double2(x, y);
+            }
+        }
+    }
+    PL_DEV uint32_t ld_word(uint32_t lo, uint32_t uo) const {
+        if constexpr (BUF) return __builtin_amdgcn_raw_buffer_load_b32(r, (int)lo, (int)uo, 0);
+        else return *reinterpret_cast<const uint32_t*>(p + lo + uo);
+    }
+    PL_DEV void st_word(uint32_t lo, uint32_t uo, uint32_t v) const {
+        if constexpr (BUF) __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)lo, (int)uo, 0);
+        else *reinterpret_cast<uint32_t*>(p + lo + uo) = v;
+    }
 };
 
 PL_DEV int field(uint64_t row, int d) { return (int)((row >> (RB * d)) & 31u); }
@@ -363,19 +459,19 @@ struct Fold {
 // (even, odd) pair to this lane's slot and continue one depth down with f.
 // Compile-time recursion keeps every pending value in a register.
 template <class G, int D>
-PL_DEV void fold(Fold<G>& st, double v, int idx, unsigned char* smem, unsigned char* ws, int plane) {
+PL_DEV void fold(Fold<G>& st, double v, int idx, unsigned char* smem, const Span<G::BUF>& ws, int plane) {
     if constexpr (D == G::n) {
         st.lam = v;
     } else {
         if (idx & 1) {
-            double2* dst = reinterpret_cast<double2*>((D >= G::DL ? smem : ws) + G::llr_off(D));
             if (G::DS != 2 || !((st.skip >> D) & 1u)) {
-                if constexpr (D < G::F + G::NTS && D < G::DL) {
-                    double2* a = dst + (idx >> 1) * 64 + plane;
-                    __builtin_nontemporal_store(st.pend[D], &a->x);
-                    __builtin_nontemporal_store(v, &a->y);
-                } else {
+                if constexpr (D >= G::DL) {
+                    double2* dst = reinterpret_cast<double2*>(smem + G::llr_off(D));
                     dst[(idx >> 1) * 64 + plane] = make_double2(st.pend[D], v);
+                } else {
+                    // the shallowest workspace depths as streaming stores (TG::NTS)
+                    ws.template st_pair<(D < G::F + G::NTS)>(plane * 16, (uint32_t)G::llr_off(D) + (idx >> 1) * 1024,
+                                                             st.pend[D], v);
                 }
             }
             fold<G, D + 1>(st, f_ms(st.pend[D], v), idx >> 1, smem, ws, plane);
@@ -388,35 +484,33 @@ PL_DEV void fold(Fold<G>& st, double v, int idx, unsigned char* smem, unsigned c
 // Right child at depth Q = P+1: g over the parent pairs (slot ps) with the left
 // sibling's partial sums, then the f-chain down to the leaf.
 template <class G, int P>
-PL_DEV double descend_g(unsigned char* smem, unsigned char* ws, int plane, int ps, int bs, uint32_t bb,
+PL_DEV double descend_g(unsigned char* smem, const Span<G::BUF>& ws, int plane, int ps, int bs, uint32_t bb,
                         uint32_t bw5, uint32_t skip) {
     constexpr int n = G::n, Q = P + 1, SQ = 1 << (n - Q);
     Fold<G> st;
     st.lam = 0.0;
     if constexpr (G::DS == 2) st.skip = skip;
-    const double2* src = reinterpret_cast<const double2*>((P >= G::DL ? smem : ws) + G::llr_off(P)) + ps;
+    constexpr bool PW = P < G::DL;  // the parent pool is in the workspace
+    const double2* src = reinterpret_cast<const double2*>(smem + (PW ? 0 : G::llr_off(P))) + ps;  // LDS parents
     uint32_t w = 0;
     if constexpr (Q > G::NB) w = beta_get<n>(Q, bb, bw5);
-    const uint32_t* bsrc = reinterpret_cast<const uint32_t*>(ws + G::bl_off(Q <= G::NB ? Q : 1)) + bs;
-    constexpr int UM = G::LCAP == 1 ? PL_SC_U : PL_LIST_U;
+    constexpr int UM = G::LCAP == 1 ? PL_SC_U : (PW && P <= G::F + 1 ? G::U_TOP : PL_LIST_U);
     constexpr int U = SQ < UM ? SQ : UM;  // parent pairs in flight
 #pragma unroll 1
     for (int t0 = 0; t0 < SQ; t0 += U) {
         // the partial-sum word first: waiting for it then leaves the pair
         // loads in flight (each pair is waited for at its own fold)
         if constexpr (Q <= G::NB) {
-            if ((t0 & 31) == 0) w = bsrc[(t0 >> 5) * 64];
+            if ((t0 & 31) == 0) w = ws.ld_word(bs * 4, (uint32_t)G::bl_off(Q <= G::NB ? Q : 1) + (t0 >> 5) * 256);
         }
         double2 pr[U];
 #pragma unroll
         for (int k = 0; k < U; ++k) {
             // the shallowest workspace depths' g reads as streaming loads (TG::NTD)
-            if constexpr (G::NTD > 0 && P < G::F + G::NTD && P < G::DL) {
-                const double2* a = src + (t0 + k) * 64;
-                pr[k] = make_double2(__builtin_nontemporal_load(&a->x), __builtin_nontemporal_load(&a->y));
-            } else {
+            if constexpr (PW)
+                pr[k] = ws.template ld_pair<(G::NTD > 0 && P < G::F + G::NTD)>(ps * 16, (uint32_t)G::llr_off(P) + (t0 + k) * 1024);
+            else
                 pr[k] = src[(t0 + k) * 64];
-            }
         }
 #pragma unroll
         for (int k = 0; k < U; ++k)
@@ -425,14 +519,29 @@ PL_DEV double descend_g(unsigned char* smem, unsigned char* ws, int plane, int p
     return st.lam;
 }
 
+// The channel rows of one frame group (FPW frames from frame f0), as the
+// descents read them.
+template <class G>
+struct Chan {
+    Span<G::BUF> rows;  // from the row of frame f0 to the end of the group's last row
+    bool near;          // wave-uniform: every row of the group starts within 2^31 bytes of the first
+    bool raw;           // wave-uniform: depth-0 pairs are read in place (fused_loop)
+    uint32_t raw_lo;    // raw: the lane's pair (lane / FPW of frame lane % FPW), bytes from rows
+    const double* own;  // no staging (SC): the row of the lane's own frame
+    uint32_t own_lo;    // and its byte offset in rows (near)
+    PL_DEV double2 pair(int k) const {  // values k, k + 1 of the lane's row (k even)
+        if (G::BUF && near) return rows.ld_pair(own_lo, k * 8);
+        return make_double2(own[k], own[k + 1]);
+    }
+};
+
 // Fused top from staged depth D0 (0 = channel; 1, 2 = the path-independent
 // left-most f-only nodes, valid when the ancestors at depths 1..D0 are left
 // children): depth-F elements from 2^(F-D0) values each (level d is g where the
 // depth-d ancestor of leaf i is a right child), then the f-chain to the leaf.
 template <class G, int D0>
-PL_DEV double fused_loop(unsigned char* smem, unsigned char* ws, int lane, int fw, int plane, const double* ch,
-                         const double2* raw, const bool* right, const uint32_t* const* bsrc, uint32_t* bw,
-                         uint32_t skip) {
+PL_DEV double fused_loop(unsigned char* smem, const Span<G::BUF>& ws, int lane, int fw, int plane, const Chan<G>& ch,
+                         const bool* right, const uint32_t* bsl, uint32_t* bw, uint32_t skip) {
     constexpr int n = G::n, F = G::F, SF = 1 << (n - F), W = 1 << (F - D0);
     Fold<G> st;
     st.lam = 0.0;
@@ -444,18 +553,20 @@ PL_DEV double fused_loop(unsigned char* smem, unsigned char* ws, int lane, int f
         // frame's LCAP lanes all fetching the same pairs), parks the chunk in
         // the metric/row scratch (idle during a descend) and every lane reads
         // its frame's pairs back as LDS broadcasts.  Next chunk prefetched.
-        constexpr int CH = 1;  // pairs per lane per chunk (CH = 2: 7.5 ms against 7.06)
+        constexpr int CH = G::FT_CH;  // pairs per lane per chunk (TG::WIDE; with flat addresses CH = 2: 7.5 ms against 7.06)
         constexpr int PPI = W / 2, IPC = CH * G::LCAP / PPI, NCH = SF / IPC;
         // depth 0 straight from the input rows when they are 16-byte aligned
         // (`raw`: pair lane / FPW of frame lane % FPW; chunk c at + c * LCAP):
         // the same 8 lines per chunk as the staged copy, which is then not stored
-        const bool from_raw = D0 == 0 && raw != nullptr;
-        const double2* src = from_raw ? raw : reinterpret_cast<const double2*>(ws + G::st_off(D0)) + lane;
+        const bool from_raw = D0 == 0 && ch.raw;
+        const Span<G::BUF> src = from_raw ? ch.rows : ws;
+        const uint32_t srcl = from_raw ? ch.raw_lo : (uint32_t)lane * 16;
+        const uint32_t srcu = from_raw ? 0u : (uint32_t)G::st_off(D0);
         const int cstr = from_raw ? G::LCAP : 64;
         double2* stg = reinterpret_cast<double2*>(smem + G::L_MET);
         double2 nxt[CH];
 #pragma unroll
-        for (int h = 0; h < CH; ++h) nxt[h] = src[h * cstr];
+        for (int h = 0; h < CH; ++h) nxt[h] = src.ld_pair(srcl, srcu + h * cstr * 16);
 #pragma unroll 1
         for (int c = 0; c < NCH; ++c) {
             lds_sync();  // the previous chunk's reads are issued before the overwrite
@@ -470,7 +581,8 @@ PL_DEV double fused_loop(unsigned char* smem, unsigned char* ws, int lane, int f
             for (int d = D0 + 1; d <= F; ++d) {
                 static_assert(32 % (IPC << (F - D0 - 1)) == 0, "a chunk's elements share one partial-sum word per depth");
                 const int e0 = (c * IPC) << (F - d);
-                if (d <= G::NB && right[d] && (e0 & 31) == 0) bw[d] = bsrc[d][(e0 >> 5) * 64];
+                if (d <= G::NB && right[d] && (e0 & 31) == 0)
+                    bw[d] = ws.ld_word(bsl[d], (uint32_t)G::bl_off(d <= G::NB ? d : 1) + (e0 >> 5) * 256);
             }
             // the next chunk's prefetch: unconditional (the last chunk re-reads
             // itself; a conditional one made the compiler's wait for the words
@@ -480,12 +592,10 @@ PL_DEV double fused_loop(unsigned char* smem, unsigned char* ws, int lane, int f
                 const int cn = c + 1 < NCH ? c + 1 : c;
 #pragma unroll
                 for (int h = 0; h < CH; ++h) {
-                    if constexpr (PL_NT_CH) {
-                        const double2* a = src + (cn * CH + h) * cstr;
-                        nxt[h] = make_double2(__builtin_nontemporal_load(&a->x), __builtin_nontemporal_load(&a->y));
-                    } else {
-                        nxt[h] = src[(cn * CH + h) * cstr];
-                    }
+                    // (the last chunk's unused re-read fetches one pair per lane,
+                    // as with CH = 1: re-reading both cost 0.2 % more HBM-side bytes)
+                    const int hn = c + 1 < NCH ? h : 0;
+                    nxt[h] = src.template ld_pair<(PL_NT_CH != 0)>(srcl, srcu + (cn * CH + hn) * cstr * 16);
                 }
             };
             // no inner loop (IPC <= UNR): issued here.  Otherwise (LCAP >= 16)
@@ -493,7 +603,7 @@ PL_DEV double fused_loop(unsigned char* smem, unsigned char* ws, int lane, int f
             // vmcnt(0) for the words above and would drain a prefetch issued
             // before it (L = 16 -2.3 %, L = 32 -1 %; at LCAP = 8, whose inner
             // loops are the short D0 = 1, 2 passes, +3 %: spills).
-            constexpr bool PF_IN = IPC > UNR && G::LCAP >= 16;
+            constexpr bool PF_IN = IPC > UNR && G::FT_PF_IN;
             if constexpr (!PF_IN) prefetch();
             lds_sync();
             // (unrolled 2, 4 at LCAP = 16: the D0 = 0 chunks (IPC = 2, 4) run
@@ -530,7 +640,6 @@ PL_DEV double fused_loop(unsigned char* smem, unsigned char* ws, int lane, int f
         }
         return st.lam;
     }
-    const double2* src = reinterpret_cast<const double2*>(ws + G::st_off(D0)) + fw;
     constexpr int kChUnroll = G::LCAP == 1 ? PL_SC_FUNROLL : 2;
 #pragma unroll kChUnroll
     for (int t = 0; t < SF; ++t) {
@@ -538,20 +647,25 @@ PL_DEV double fused_loop(unsigned char* smem, unsigned char* ws, int lane, int f
         if constexpr (G::STAGE) {
 #pragma unroll
             for (int k = 0; k < W / 2; ++k) {
-                const double2 pr = src[((t * (W / 2)) + k) * G::FPW];
+                const double2 pr = ws.ld_pair(fw * 16, (uint32_t)G::st_off(D0) + ((t * (W / 2)) + k) * G::FPW * 16);
                 v[2 * k] = pr.x;
                 v[2 * k + 1] = pr.y;
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < W; ++k) v[k] = ch[t * W + k];
+            for (int k = 0; k < W; k += 2) {
+                const double2 pr = ch.pair(t * W + k);
+                v[k] = pr.x;
+                v[k + 1] = pr.y;
+            }
         }
 #pragma unroll
         for (int d = D0 + 1; d <= F; ++d) {
             const int e0 = t << (F - d);  // depth-d element index of v[0]
             const int m = 1 << (F - d);
             if (right[d]) {
-                if (d <= G::NB && (e0 & 31) == 0) bw[d] = bsrc[d][(e0 >> 5) * 64];
+                if (d <= G::NB && (e0 & 31) == 0)
+                    bw[d] = ws.ld_word(bsl[d], (uint32_t)G::bl_off(d <= G::NB ? d : 1) + (e0 >> 5) * 256);
                 const uint32_t b = bw[d] >> (e0 & 31);
 #pragma unroll
                 for (int k = 0; k < m; ++k) v[k] = g_op(v[2 * k], v[2 * k + 1], b >> k);
@@ -566,30 +680,28 @@ PL_DEV double fused_loop(unsigned char* smem, unsigned char* ws, int lane, int f
 }
 
 template <class G>
-PL_DEV double descend_fused(unsigned char* smem, unsigned char* ws, int lane, int fw, int plane, int i,
-                            const double* ch, const double2* raw, uint64_t brow, uint32_t bb, uint32_t bw5,
-                            uint32_t skip = 0) {
+PL_DEV double descend_fused(unsigned char* smem, const Span<G::BUF>& ws, int lane, int fw, int plane, int i,
+                            const Chan<G>& ch, uint64_t brow, uint32_t bb, uint32_t bw5, uint32_t skip = 0) {
     constexpr int n = G::n, F = G::F;
     bool right[F + 1];
-    const uint32_t* bsrc[F + 1];
+    uint32_t bsl[F + 1];  // the lane's byte offset in the partial-sum pool of depth d
     uint32_t bw[F + 1];
 #pragma unroll
     for (int d = 1; d <= F; ++d) {
         right[d] = (i >> (n - d)) & 1;
-        bsrc[d] = reinterpret_cast<const uint32_t*>(ws + G::bl_off(d <= G::NB ? d : 1)) +
-                  G::pl(field(brow, d), fw);
+        bsl[d] = (uint32_t)G::pl(field(brow, d), fw) * 4;
         bw[d] = (d > G::NB) ? beta_get<n>(d, bb, bw5) : 0u;
     }
     if constexpr (G::NS >= 3) {
-        if (!right[1] && !right[2] && !right[3]) return fused_loop<G, 3>(smem, ws, lane, fw, plane, ch, raw, right, bsrc, bw, skip);
+        if (!right[1] && !right[2] && !right[3]) return fused_loop<G, 3>(smem, ws, lane, fw, plane, ch, right, bsl, bw, skip);
     }
     if constexpr (G::NS >= 2) {
-        if (!right[1] && !right[2]) return fused_loop<G, 2>(smem, ws, lane, fw, plane, ch, raw, right, bsrc, bw, skip);
+        if (!right[1] && !right[2]) return fused_loop<G, 2>(smem, ws, lane, fw, plane, ch, right, bsl, bw, skip);
     }
     if constexpr (G::NS >= 1) {
-        if (!right[1]) return fused_loop<G, 1>(smem, ws, lane, fw, plane, ch, raw, right, bsrc, bw, skip);
+        if (!right[1]) return fused_loop<G, 1>(smem, ws, lane, fw, plane, ch, right, bsl, bw, skip);
     }
-    return fused_loop<G, 0>(smem, ws, lane, fw, plane, ch, raw, right, bsrc, bw, skip);
+    return fused_loop<G, 0>(smem, ws, lane, fw, plane, ch, right, bsl, bw, skip);
 }
 
 // Size 2^k (k <= 3) of the rate-0 node (all leaves frozen) whose first leaf is
@@ -628,14 +740,17 @@ PL_DEV void rate0_leaves(const double* A, double* out) {
 // stored (this lane's plane); their path-metric increments (bit 0) are added
 // in leaf order.  SC: nothing to evaluate.
 template <class G, int K, bool SC>
-PL_DEV void rate0_rest(const unsigned char* smem, const unsigned char* ws, int plane, bool active, double& pm) {
+PL_DEV void rate0_rest(const unsigned char* smem, const Span<G::BUF>& ws, int plane, bool active, double& pm) {
     if constexpr (!SC) {
         constexpr int S = 1 << K, D = G::n - K;
-        const double2* src = reinterpret_cast<const double2*>((D >= G::DL ? smem : ws) + G::llr_off(D)) + plane;
+        constexpr bool PW = D < G::DL;  // the node's array is in the workspace
+        const double2* src = reinterpret_cast<const double2*>(smem + (PW ? 0 : G::llr_off(D))) + plane;
         double a[S], ll[S];
 #pragma unroll
         for (int j = 0; j < S / 2; ++j) {
-            const double2 pr = src[j * 64];
+            double2 pr;
+            if constexpr (PW) pr = ws.ld_pair(plane * 16, (uint32_t)G::llr_off(D) + j * 1024);
+            else pr = src[j * 64];
             a[2 * j] = pr.x;
             a[2 * j + 1] = pr.y;
         }
@@ -663,7 +778,7 @@ PL_DEV void rate0_rest(const unsigned char* smem, const unsigned char* ws, int p
 }
 
 template <class G, int P>
-PL_DEV double descend_from(int p, unsigned char* smem, unsigned char* ws, int plane, int ps, int bs, uint32_t bb,
+PL_DEV double descend_from(int p, unsigned char* smem, const Span<G::BUF>& ws, int plane, int ps, int bs, uint32_t bb,
                            uint32_t bw5, uint32_t skip = 0) {
     if constexpr (P >= G::n) {
         return 0.0;
@@ -703,7 +818,8 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
     // every pruning (same rows, partial sums and bit; metric -inf), uses slot
     // 0's plane, and so loads the lines slot 0 loads and stores the values
     // slot 0 stores to the same addresses -- no memory traffic of its own.
-    unsigned char* const ws = workspace + (size_t)blockIdx.x * G::WS;
+    // the wave's own slice, and nothing past it
+    const Span<G::BUF> ws(workspace + (size_t)blockIdx.x * G::WS, (uint32_t)G::WS);
     uint64_t own = 0;
 #pragma unroll
     for (int d = 0; d < 12; ++d) own |= (uint64_t)slot << (RB * d);
@@ -711,7 +827,8 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
     uint64_t* const rowx = reinterpret_cast<uint64_t*>(smem + G::L_ROW + fw * G::GS);  // [LCAP][2]
     uint64_t* const brx = reinterpret_cast<uint64_t*>(smem + G::L_BR) + base;          // [LCAP]
     uint32_t* const surv = reinterpret_cast<uint32_t*>(smem + G::L_SURV) + base;       // [LCAP]
-    uint32_t* const walk0 = reinterpret_cast<uint32_t*>(ws + G::W_WALK) + (G::SHADOW ? fw : 0);  // [2][CW][64]
+    // the lane's byte offset in the walk buffers ([2][CW][64] u32 at W_WALK) as path slot s
+    auto walk_lo = [&](int s) { return (uint32_t)(G::SHADOW ? s * FPW + fw : lane) * 4; };
 
     unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // STAMPS: metric evaluations -- [0] path_metrics_fast calls (per wave), [1] of
@@ -753,8 +870,13 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
         const int64_t f0 = grp * FPW;
         const int64_t frame = f0 + fw;
         const bool live = frame < batch;
-        const double* __restrict__ ch = llr + (live ? frame : batch - 1) * ld;
-        const double2* raw = nullptr;  // depth-0 pairs read in place (fused_loop)
+        // Channel rows relative to the row of frame f0 (64-bit scalar
+        // arithmetic: inputs of any size); a lane's row starts (its frame -
+        // f0) * ld doubles in, dead lanes clamped to frame batch - 1.
+        const int64_t nfr = batch - f0 < FPW ? batch - f0 : FPW;  // frames of this group
+        const bool near = ld >= 0 && (uint64_t)ld * (8u * FPW) < (1ull << 31);
+        Chan<G> ch{Span<G::BUF>(llr + f0 * ld, near ? (uint32_t)(((nfr - 1) * ld + N) * 8) : 0u), near, false, 0u,
+                   llr + (live ? frame : batch - 1) * ld, (uint32_t)((live ? fw : nfr - 1) * ld * 8)};
         if constexpr (G::STAGE) {
             // channel rows of this wave's frames -> [N/2][FPW] pairs, plus the
             // path-independent left-most f-only nodes of depths 1..NS.
@@ -762,8 +884,11 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
             const int sf = lane % FPW;
             const int64_t fr = f0 + sf < batch ? f0 + sf : batch - 1;
             const double* row = llr + fr * ld;
-            if (G::dedup(0) && (ld & 1) == 0 && ((uintptr_t)llr & 15) == 0)
-                raw = reinterpret_cast<const double2*>(row) + lane / FPW;
+            const uint32_t row_lo = (uint32_t)((fr - f0) * ld * 8);  // near
+            if (G::dedup(0) && near && (ld & 1) == 0 && ((uintptr_t)llr & 15) == 0) {
+                ch.raw = true;
+                ch.raw_lo = row_lo + (lane / FPW) * 16;
+            }
             constexpr int CV = 2 << G::NS;    // channel values per lane per step
             constexpr int CPI = 64 / FPW;     // chunks per frame per step
             // NaN path metrics need a NaN LLR at a leaf, i.e. a NaN input or an
@@ -783,17 +908,27 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                 const int cc = cb + lane / FPW;
                 double v[CV];
 #pragma unroll
-                for (int k = 0; k < CV; ++k) v[k] = row[CV * cc + k];
+                for (int k = 0; k < CV; k += 2) {
+                    if (G::BUF && near) {  // (16-byte loads of 8-byte aligned rows, as the flat loads are)
+                        const double2 pr = ch.rows.ld_pair(row_lo + (lane / FPW) * (CV * 8), (cb * CV + k) * 8);
+                        v[k] = pr.x;
+                        v[k + 1] = pr.y;
+                    } else {
+                        v[k] = row[CV * cc + k];
+                        v[k + 1] = row[CV * cc + k + 1];
+                    }
+                }
 #pragma unroll
                 for (int k = 0; k < CV; ++k) ext += !(fabs(v[k]) < 0x1p1000) ? (__builtin_isnan(v[k]) ? 2 : 1) : 0;
                 // depth d of the chunk: CV >> d values = CV >> (d+1) pairs
 #pragma unroll
                 for (int d = 0; d <= G::NS; ++d) {
-                    double2* dst = reinterpret_cast<double2*>(ws + G::st_off(d)) + sf;
                     const int np = CV >> (d + 1);
-                    if (d > 0 || raw == nullptr) {
+                    if (d > 0 || !ch.raw) {
 #pragma unroll
-                        for (int k = 0; k < np; ++k) dst[(np * cc + k) * FPW] = make_double2(v[2 * k], v[2 * k + 1]);
+                        for (int k = 0; k < np; ++k)
+                            ws.st_pair((sf + np * (lane / FPW) * FPW) * 16, (uint32_t)G::st_off(d) + (np * cb + k) * FPW * 16,
+                                       v[2 * k], v[2 * k + 1]);
                     }
                     if (d < G::NS) {
 #pragma unroll
@@ -874,7 +1009,7 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                 if (dstart <= DL) ws_sync();  // workspace written by other lanes
                 STAMP(7);
                 if (dstart <= F) {
-                    lam = descend_fused<G>(smem, ws, lane, fw, plane, i, ch, raw, brow, bb, bw5, dskip);
+                    lam = descend_fused<G>(smem, ws, lane, fw, plane, i, ch, brow, bb, bw5, dskip);
                     lrow = set_range(lrow, (!G::SHADOW || slot < nact) ? own : 0ull, F, n);
                     STAMP(0);
                 } else {
@@ -1140,8 +1275,8 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                     // the node is a left child at a multi-word depth: store its
                     // zero words as that depth's partial sums (read by the right
                     // sibling's g), nothing to combine
-                    uint32_t* dst = reinterpret_cast<uint32_t*>(ws + G::bl_off(dd)) + G::pl(slot, fw);
-                    for (int w = 0; w < (1 << (skipK - 5)); ++w) dst[w * 64] = 0u;
+                    for (int w = 0; w < (1 << (skipK - 5)); ++w)
+                        ws.st_word(G::pl(slot, fw) * 4, (uint32_t)G::bl_off(dd) + w * 256, 0u);
                     brow = set_field(brow, dd, slot);
                     k = steps + 1;  // done (no register store either)
                 }
@@ -1160,42 +1295,45 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                     // Planes from the list size after this leaf's pruning: a lane that
                     // just stopped shadowing slot 0 writes its own.
                     const int wslot = (!G::SHADOW || slot < nact) ? slot : 0;
-                    uint32_t* const walkw = walk0 + (G::SHADOW ? wslot * FPW : lane);
+                    const uint32_t walkl = walk_lo(wslot);
                     int parity = 0;
                     ws_sync();  // multi-word betas of other lanes live in the workspace
-                    walkw[0] = cur;
+                    ws.st_word(walkl, (uint32_t)G::W_WALK, cur);
                     if (SC && skipK > 5) {  // the skipped node's zero words (k = skipK)
-                        for (int w = 1; w < (1 << (skipK - 5)); ++w) walkw[w * 64] = 0u;
+                        for (int w = 1; w < (1 << (skipK - 5)); ++w) ws.st_word(walkl, (uint32_t)G::W_WALK + w * 256, 0u);
                     }
                     for (; k < steps; ++k) {
                         const int cwc = 1 << (k - 5);
                         const int ls = G::pl(field(brow, dd <= G::NB ? dd : 0), fw);
                         const bool last = (k + 1 == steps);
-                        const uint32_t* lsrc = reinterpret_cast<const uint32_t*>(ws + G::bl_off(dd <= G::NB ? dd : 1)) + ls;
-                        uint32_t* ldst = reinterpret_cast<uint32_t*>(ws + G::bl_off(dd - 1 >= 1 ? dd - 1 : 1)) +
-                                         G::pl(wslot, fw);
+                        const uint32_t lsrcu = (uint32_t)G::bl_off(dd <= G::NB ? dd : 1);
                         // word j of the step's input gives output words 2j, 2j+1
                         // (one round trip per input word instead of per output
                         // word; batching WB = 2 / 4 input words measured 7 / 16 %
                         // slower at L = 8: spills)
                         constexpr int WB = 1;
-                        uint32_t* const wdst = (last && dd - 1 > 0) ? ldst : walkw + (parity ^ 1) * G::CW * 64;
+                        // the last step's words go to the pool of depth dd - 1 (this lane's slot)
+                        const bool to_pool = last && dd - 1 > 0;
+                        const uint32_t wdstl = to_pool ? (uint32_t)G::pl(wslot, fw) * 4 : walkl;
+                        const uint32_t wdstu = to_pool ? (uint32_t)G::bl_off(dd - 1 >= 1 ? dd - 1 : 1)
+                                                       : (uint32_t)G::W_WALK + (parity ^ 1) * G::CW * 256;
 #pragma unroll 1
                         for (int j0 = 0; j0 < cwc; j0 += WB) {
                             uint32_t cv[WB], lv[WB];
 #pragma unroll
                             for (int u = 0; u < WB; ++u) {
                                 if (j0 + u < cwc) {  // wave-uniform
-                                    cv[u] = walkw[(parity * G::CW + j0 + u) * 64];
-                                    lv[u] = (dd > G::NB) ? bw5 : lsrc[(j0 + u) * 64];
+                                    cv[u] = ws.ld_word(walkl, (uint32_t)G::W_WALK + (parity * G::CW + j0 + u) * 256);
+                                    lv[u] = (dd > G::NB) ? bw5 : ws.ld_word(ls * 4, lsrcu + (j0 + u) * 256);
                                 }
                             }
 #pragma unroll
                             for (int u = 0; u < WB; ++u) {
                                 if (j0 + u < cwc) {
                                     const uint32_t x = lv[u] ^ cv[u];
-                                    wdst[(2 * (j0 + u)) * 64] = spread16(x) | (spread16(cv[u]) << 1);
-                                    wdst[(2 * (j0 + u) + 1) * 64] = spread16(x >> 16) | (spread16(cv[u] >> 16) << 1);
+                                    ws.st_word(wdstl, wdstu + (2 * (j0 + u)) * 256, spread16(x) | (spread16(cv[u]) << 1));
+                                    ws.st_word(wdstl, wdstu + (2 * (j0 + u) + 1) * 256,
+                                               spread16(x >> 16) | (spread16(cv[u] >> 16) << 1));
                                 }
                             }
                         }
@@ -1211,7 +1349,7 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
         }
 
         // ================================================ best path, output
-        uint32_t* const walk = walk0 + (G::SHADOW ? (slot < nact ? slot : 0) * FPW : lane);
+        const uint32_t walkl = walk_lo(slot < nact ? slot : 0);
         int best = 0;
         if constexpr (!SC) {
             met[slot] = make_double2(pm, 0.0);
@@ -1220,7 +1358,8 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                 // CRC-aided selection (build-defined extension): the
                 // first path in descending-metric order (ties: lower slot) whose
                 // u_hat[info] passes the CRC; none -> that order's first = argmax
-                const uint32_t crc = crc_of_xhat(walk + root_par * G::CW * 64, 64, G::CW, crc_g);
+                const uint32_t crc = crc_of_xhat(
+                    reinterpret_cast<const uint32_t*>(ws.p + G::W_WALK + walkl) + root_par * G::CW * 64, 64, G::CW, crc_g);
                 int rank = 0;
                 for (int q = 0; q < nact; ++q) {
                     const double v = met[q].x;
@@ -1255,13 +1394,14 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
             for (int w0 = 0; w0 < G::CW; w0 += XB) {
                 uint32_t xw[XB];
 #pragma unroll
-                for (int w = 0; w < XB; ++w) xw[w] = walk[(root_par * G::CW + w0 + w) * 64];
+                for (int w = 0; w < XB; ++w) xw[w] = ws.ld_word(walkl, (uint32_t)G::W_WALK + (root_par * G::CW + w0 + w) * 256);
                 asm volatile("" ::: "memory");
 #pragma unroll
                 for (int w = 0; w < XB; ++w) X[w0 + w] = polar_word_transform(xw[w]);
             }
             } else {
-            for (int w = 0; w < G::CW; ++w) X[w] = polar_word_transform(walk[(root_par * G::CW + w) * 64]);
+            for (int w = 0; w < G::CW; ++w)
+                X[w] = polar_word_transform(ws.ld_word(walkl, (uint32_t)G::W_WALK + (root_par * G::CW + w) * 256));
             }
         }
         lds_sync();
