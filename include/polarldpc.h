@@ -685,6 +685,90 @@ int pl_ldpc_rate_match(const pl_rate_match* rm, const uint8_t* cw_dev, int64_t l
 int pl_ldpc_rate_recover(const pl_rate_match* rm, const void* llr_dev, int64_t ld_llr, int64_t batch, void* out_dev,
                          int64_t ld_out, int32_t n_out, double filler_llr, int32_t flags, void* stream);
 
+/* ---- Rate matching for polar codes: puncture, shorten, repeat -----------------------
+ * Which of the N bits of a codeword x = u F^(x)n (natural order, pl_polar_encode) are
+ * transmitted, and how E received LLRs come back to the N decoder inputs.  This
+ * comment is the definition; the kernels (polar_ratematch.hip),
+ * polar.PolarRateMatcher and the harness cite it.
+ * Parameters and conditions; a violation is PL_EINVAL naming the first one violated,
+ * in this order:
+ *   1. N is a power of two in 2 .. 32768
+ *   2. 1 <= E <= 2^30
+ *   3. mode is PL_PRM_PUNCTURE or PL_PRM_SHORTEN (checked always, used when E < N)
+ *   4. nsub is a power of two in 1 .. 32, and nsub <= N
+ *   5. perm[0:nsub] is a permutation of 0 .. nsub-1
+ * Derived: S = N / nsub, U = max(N - E, 0), max_reps = ceil(E / N), inv the inverse
+ * of perm (entries nsub .. 31 of inv are 0), pad = 0.
+ * Interleaved sequence: y[m] = x[J(m)], J(m) = perm[m / S] S + m mod S, m = 0 .. N-1:
+ *   the N positions in nsub sub-blocks of S, the sub-blocks permuted.  The caller
+ *   supplies perm; no standard's table is reproduced.  nsub = 1 (identity) is
+ *   plain block puncturing and shortening.
+ * Selection e[t], t = 0 .. E-1:
+ *   E >= N           e[t] = y[t mod N]      (repetition)
+ *   E < N, puncture  e[t] = y[t + N - E]    (the first U of y are not sent)
+ *   E < N, shorten   e[t] = y[t]            (the last U of y are not sent; they are 0)
+ * Recovery of out[b][0:N] (fp64) from llr[b][0:E] (fp64, or fp32 with
+ * PL_PRM_LLR_F32).  Position i has interleaved index m = inv[i / S] S + i mod S.
+ *   E >= N    the terms t = m, m+N, ... < E, each converted to fp64, summed left to
+ *             right in ascending t starting from the first term (a single term is a
+ *             copy: -0.0 stays -0.0)
+ *   puncture  m < N - E: +0.0; else llr[m - (N - E)]
+ *   shorten   m < E: llr[m]; else +known_llr (the sign that decodes to bit 0:
+ *             pl_awgn_llr maps 0 -> +1); finite, so that the frame stays on the
+ *             decoders' fast path
+ *   PL_PRM_ACCUMULATE (Chase combining of retransmissions, possibly through another
+ *             matcher of the same N): a transmitted position becomes out + s, s the
+ *             value above; every other position keeps its value.
+ * The output is fp64 only: no polar decoder reads fp32.
+ * Frozen set: a shortened code is one only if the untransmitted x_i are zero for
+ * every message.  x_i = XOR of u_j over j & i == i, so that holds exactly when every
+ * u_j with j a superset of an untransmitted position is frozen:
+ * pl_polar_rate_match_forced gives that minimal set (all zero unless shorten and
+ * E < N).  THE CALLER'S OBLIGATION: the frozen mask of the plan that encodes and
+ * decodes must contain it.  polar.construct_rate_matched builds such a set.
+ * A superset of i is >= i, so when the last U of y are the U highest positions the set
+ * is those U indices alone; every lower position a permutation moves into that tail
+ * adds its supersets (the reversal at E = N/2 + 1 forces all N).  With shortening,
+ * choose perm so that the highest sub-blocks stay last.
+ * pl_polar_rate_match_check fills the derived fields and makes no device call.  The
+ * kernels take the parameters by value: there is no device object.
+ * pl_polar_rate_match and pl_polar_rate_recover derive the fields again themselves,
+ * so a caller's derived fields are never trusted. */
+#define PL_PRM_PUNCTURE 0
+#define PL_PRM_SHORTEN 1
+typedef struct {
+    int32_t N, E, mode, nsub;    /* parameters                                             */
+    uint8_t perm[32];            /* sub-block permutation, entries 0 .. nsub-1 used        */
+    int32_t S, U, max_reps, pad; /* derived: S = N / nsub, U = max(N - E, 0), ceil(E / N)  */
+    uint8_t inv[32];             /* derived: inverse permutation                           */
+} pl_polar_rm;
+int pl_polar_rate_match_check(pl_polar_rm* rm);
+/* The same from plain arguments (the check's window for tests, as pl_debug_rate_match_probe);
+ * perm: nsub bytes (may be NULL when nsub == 1: the identity). */
+int pl_debug_polar_rate_match_probe(int32_t N, int32_t E, int32_t mode, int32_t nsub, const uint8_t* perm,
+                                    pl_polar_rm* out);
+/* mask_host uint8 [N], host memory: 1 where u_j must be frozen (see "Frozen set" above), else 0.
+ * OR-zeta transform over supersets, N log N; no device call. */
+int pl_polar_rate_match_forced(const pl_polar_rm* rm, uint8_t* mask_host);
+/* e[b][t] as defined above, t < E: cw_dev uint8 [batch][ld_cw], ld_cw >= N, bytes copied as
+ * they are; e_dev uint8 [batch][ld_e], ld_e >= E, bytes beyond E are left alone.
+ * Asynchronous on `stream`; batch == 0 launches nothing.  PL_EINVAL for what
+ * pl_polar_rate_match_check refuses, a NULL pointer, batch < 0 and a short pitch; every
+ * check runs before the first device call. */
+int pl_polar_rate_match(const pl_polar_rm* rm, const uint8_t* cw_dev, int64_t ld_cw, int64_t batch, uint8_t* e_dev,
+                        int64_t ld_e, void* stream);
+#define PL_PRM_LLR_F32 1    /* llr_dev is float (else double)                          */
+#define PL_PRM_ACCUMULATE 4 /* add to the recovery out_dev already holds               */
+/* Recovery as defined above: llr_dev [batch][ld_llr], ld_llr >= E; out_dev double
+ * [batch][ld_out], ld_out >= N, elements beyond N are left alone; pitches in elements.
+ * known_llr must be finite and > 0.  Asynchronous on `stream`; batch == 0 launches
+ * nothing.  PL_EINVAL as pl_polar_rate_match, and for unknown flag bits, a known_llr
+ * that is not finite and positive, and a pointer not aligned to its element type.
+ * Both kernels cut each row at the 16-byte boundaries of its output addresses and store
+ * whole pieces 16 bytes wide, whatever the pointer and the pitch. */
+int pl_polar_rate_recover(const pl_polar_rm* rm, const void* llr_dev, int64_t ld_llr, int64_t batch, double* out_dev,
+                          int64_t ld_out, double known_llr, int32_t flags, void* stream);
+
 /* Error counting (benchmarks/ber_simulation.py:180-189):
  * counts_dev[0] += bit errors, [1] += frame errors, [2] += frames, over the
  * first `width` entries of each row.  counts_dev int64[3], device. */

@@ -32,10 +32,13 @@ EXPORTS = (
     "pl_ldpc_qc_encoder_create", "pl_ldpc_qc_encode", "pl_ldpc_qc_encoder_destroy", "pl_debug_ldpc_qc_encoder_probe",
     "pl_debug_set_qc_encoder_device", "pl_ldpc_rate_match_check", "pl_debug_rate_match_probe", "pl_ldpc_rate_match",
     "pl_ldpc_rate_recover", "pl_ldpc_qc_fixed_plan_create", "pl_ldpc_decode_i8", "pl_llr_quantize",
-    "pl_debug_ldpc_qc_fixed_plan_probe",
+    "pl_debug_ldpc_qc_fixed_plan_probe", "pl_polar_rate_match_check", "pl_debug_polar_rate_match_probe",
+    "pl_polar_rate_match_forced", "pl_polar_rate_match", "pl_polar_rate_recover",
 )
 PL_QUANT_LLR_F32 = 1  # pl_llr_quantize flag: llr_dev is float (else double)
 PL_RM_LLR_F32, PL_RM_OUT_F32, PL_RM_ACCUMULATE = 1, 2, 4  # pl_ldpc_rate_recover flags
+PL_PRM_PUNCTURE, PL_PRM_SHORTEN = 0, 1  # pl_polar_rm.mode
+PL_PRM_LLR_F32, PL_PRM_ACCUMULATE = 1, 4  # pl_polar_rate_recover flags
 
 
 class PlanInfo(ctypes.Structure):
@@ -89,6 +92,12 @@ class RateMatch(ctypes.Structure):
                                               "n", "k", "P", "M", "c0", "hi", "max_reps")]
 
 
+class PolarRateMatch(ctypes.Structure):
+    """pl_polar_rm: the parameters of a polar rate matching and the fields pl_polar_rate_match_check derives."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("N", "E", "mode", "nsub")] + [("perm", ctypes.c_uint8 * 32)] + \
+               [(f, ctypes.c_int32) for f in ("S", "U", "max_reps", "pad")] + [("inv", ctypes.c_uint8 * 32)]
+
+
 def _load(path=LIB_PATH):
     if not os.path.exists(path):
         raise ImportError(
@@ -122,6 +131,11 @@ def _load(path=LIB_PATH):
     L.pl_debug_rate_match_probe.argtypes = [I32] * 8 + [ctypes.POINTER(RateMatch)]
     L.pl_ldpc_rate_match.argtypes = [ctypes.POINTER(RateMatch), P, I64, I64, P, I64, P]
     L.pl_ldpc_rate_recover.argtypes = [ctypes.POINTER(RateMatch), P, I64, I64, P, I64, I32, D, I32, P]
+    L.pl_polar_rate_match_check.argtypes = [ctypes.POINTER(PolarRateMatch)]
+    L.pl_debug_polar_rate_match_probe.argtypes = [I32] * 4 + [P, ctypes.POINTER(PolarRateMatch)]
+    L.pl_polar_rate_match_forced.argtypes = [ctypes.POINTER(PolarRateMatch), P]
+    L.pl_polar_rate_match.argtypes = [ctypes.POINTER(PolarRateMatch), P, I64, I64, P, I64, P]
+    L.pl_polar_rate_recover.argtypes = [ctypes.POINTER(PolarRateMatch), P, I64, I64, P, I64, D, I32, P]
     L.pl_ldpc_decode_soft.argtypes = [P, P, I64, I64, P, P, P, I64, P]
     L.pl_ldpc_decode_f32.argtypes = [P, P, I64, I64, P, P, P, I64, P, I64, P]
     L.pl_decode.argtypes = [P, P, I64, I64, P, P, P]
@@ -500,6 +514,38 @@ def rate_recover(rm: RateMatch, llr: "torch.Tensor", out: "torch.Tensor", n_out:
         | (PL_RM_ACCUMULATE if accumulate else 0)
     check(lib.pl_ldpc_rate_recover(ctypes.byref(rm), llr.data_ptr(), _ld(llr), llr.shape[0], out.data_ptr(), _ld(out),
                                    int(n_out), float(filler_llr), flags, _stream(stream)), "pl_ldpc_rate_recover")
+
+
+def polar_rate_match_probe(N: int, E: int, mode: int, perm) -> PolarRateMatch:
+    """pl_debug_polar_rate_match_probe: the checked parameters with the derived fields (no device call); perm:
+    the sub-block permutation, nsub = len(perm) entries.  AssertionError with the first violated condition."""
+    p = np.ascontiguousarray(perm, dtype=np.uint8).ravel()
+    rm = PolarRateMatch()
+    check(lib.pl_debug_polar_rate_match_probe(int(N), int(E), int(mode), len(p), p.ctypes.data_as(ctypes.c_void_p),
+                                              ctypes.byref(rm)), "pl_debug_polar_rate_match_probe")
+    return rm
+
+
+def polar_rate_match_forced(rm: PolarRateMatch) -> np.ndarray:
+    """pl_polar_rate_match_forced: uint8 [N], 1 where u_j must be frozen (no device call)."""
+    mask = np.zeros(rm.N, dtype=np.uint8)
+    check(lib.pl_polar_rate_match_forced(ctypes.byref(rm), mask.ctypes.data_as(ctypes.c_void_p)),
+          "pl_polar_rate_match_forced")
+    return mask
+
+
+def polar_rate_match(rm: PolarRateMatch, cw: "torch.Tensor", e: "torch.Tensor", stream=None):
+    """pl_polar_rate_match: cw uint8 [B, >= N], e uint8 [B, >= E]: device tensors, unit inner stride, any row pitch."""
+    check(lib.pl_polar_rate_match(ctypes.byref(rm), cw.data_ptr(), _ld(cw), cw.shape[0], e.data_ptr(), _ld(e),
+                                  _stream(stream)), "pl_polar_rate_match")
+
+
+def polar_rate_recover(rm: PolarRateMatch, llr: "torch.Tensor", out: "torch.Tensor", known_llr: float,
+                       accumulate: bool = False, stream=None):
+    """pl_polar_rate_recover: llr float64 or float32 [B, >= E], out float64 [B, >= N] on the device."""
+    flags = (PL_PRM_LLR_F32 if llr.dtype == torch.float32 else 0) | (PL_PRM_ACCUMULATE if accumulate else 0)
+    check(lib.pl_polar_rate_recover(ctypes.byref(rm), llr.data_ptr(), _ld(llr), llr.shape[0], out.data_ptr(), _ld(out),
+                                    float(known_llr), flags, _stream(stream)), "pl_polar_rate_recover")
 
 
 def random_bits(seed: int, frame_offset: int, bits: "torch.Tensor", stream=None):

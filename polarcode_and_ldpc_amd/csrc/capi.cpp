@@ -1325,6 +1325,96 @@ extern "C" int pl_ldpc_rate_recover(const pl_rate_match* in, const void* llr, in
     return err == hipSuccess ? PL_OK : hipfail(err, "rate recover launch");
 }
 
+// ---- rate matching of polar codes (polar_ratematch.hip); the definition: include/polarldpc.h, pl_polar_rm ----
+extern "C" int pl_polar_rate_match_check(pl_polar_rm* rm) {
+    if (!rm) return fail(PL_EINVAL, "rate match is NULL");
+    const auto S = [](int64_t v) { return std::to_string(v); };
+    const int64_t N = rm->N, E = rm->E, nsub = rm->nsub;
+    if (N < 2 || N > 32768 || (N & (N - 1))) return fail(PL_EINVAL, "N = " + S(N) + " must be a power of 2 in 2 .. 32768");
+    if (E < 1 || E > ((int64_t)1 << 30)) return fail(PL_EINVAL, "E = " + S(E) + " outside 1 .. 2^30");
+    if (rm->mode != PL_PRM_PUNCTURE && rm->mode != PL_PRM_SHORTEN)
+        return fail(PL_EINVAL, "mode = " + S(rm->mode) + " must be PL_PRM_PUNCTURE (0) or PL_PRM_SHORTEN (1)");
+    if (nsub < 1 || nsub > 32 || (nsub & (nsub - 1)) || nsub > N)
+        return fail(PL_EINVAL, "nsub = " + S(nsub) + " must be a power of 2 in 1 .. 32 and <= N = " + S(N));
+    uint8_t inv[32] = {};
+    uint32_t seen = 0;
+    for (int64_t q = 0; q < nsub; ++q) {
+        const uint32_t v = rm->perm[q];
+        if (v >= nsub || (seen >> v & 1u))
+            return fail(PL_EINVAL, "perm[0:nsub] is no permutation of 0 .. nsub-1 = " + S(nsub - 1) + " (perm[" + S(q) +
+                                       "] = " + S(v) + ")");
+        seen |= 1u << v;
+        inv[v] = (uint8_t)q;
+    }
+    rm->S = (int32_t)(N / nsub);
+    rm->U = (int32_t)(E < N ? N - E : 0);
+    rm->max_reps = (int32_t)((E + N - 1) / N);
+    rm->pad = 0;
+    std::memcpy(rm->inv, inv, sizeof inv);
+    return PL_OK;
+}
+
+extern "C" int pl_debug_polar_rate_match_probe(int32_t N, int32_t E, int32_t mode, int32_t nsub, const uint8_t* perm,
+                                               pl_polar_rm* out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    pl_polar_rm rm{};
+    rm.N = N; rm.E = E; rm.mode = mode; rm.nsub = nsub;
+    if (perm && nsub >= 1 && nsub <= 32) std::memcpy(rm.perm, perm, (size_t)nsub);
+    if (int rc = pl_polar_rate_match_check(&rm)) return rc;
+    *out = rm;
+    return PL_OK;
+}
+
+extern "C" int pl_polar_rate_match_forced(const pl_polar_rm* in, uint8_t* mask) {
+    if (!in) return fail(PL_EINVAL, "rate match is NULL");
+    pl_polar_rm rm = *in;
+    if (int rc = pl_polar_rate_match_check(&rm)) return rc;
+    if (!mask) return fail(PL_EINVAL, "mask_host is NULL");
+    std::memset(mask, 0, (size_t)rm.N);
+    if (rm.mode != PL_PRM_SHORTEN || rm.E >= rm.N) return PL_OK;
+    for (int32_t m = rm.E; m < rm.N; ++m) mask[rm.perm[m / rm.S] * rm.S + m % rm.S] = 1;  // x_J(m) is not sent
+    // OR over subsets: afterwards mask[j] = 1 iff j is a superset of a position that is not sent
+    for (int32_t b = 1; b < rm.N; b <<= 1)
+        for (int32_t j = 0; j < rm.N; ++j)
+            if (j & b) mask[j] |= mask[j ^ b];
+    return PL_OK;
+}
+
+// the caller's parameters, checked and derived afresh; every check comes before the first device call
+static int polar_rate_match_args(const pl_polar_rm* in, pl_polar_rm* rm, const void* a, const void* b, int64_t batch) {
+    if (!in) return fail(PL_EINVAL, "rate match is NULL");
+    *rm = *in;
+    if (int rc = pl_polar_rate_match_check(rm)) return rc;
+    if (!a || !b) return fail(PL_EINVAL, "device pointers must not be NULL");
+    if (batch < 0) return fail(PL_EINVAL, "batch must be >= 0");
+    return PL_OK;
+}
+
+extern "C" int pl_polar_rate_match(const pl_polar_rm* in, const uint8_t* cw, int64_t ld_cw, int64_t batch, uint8_t* e,
+                                   int64_t ld_e, void* stream) {
+    pl_polar_rm rm;
+    if (int rc = polar_rate_match_args(in, &rm, cw, e, batch)) return rc;
+    if (ld_cw < rm.N) return fail(PL_EINVAL, "ld_cw < N = " + std::to_string(rm.N));
+    if (ld_e < rm.E) return fail(PL_EINVAL, "ld_e < E = " + std::to_string(rm.E));
+    const hipError_t err = pl::polar_rate_match_launch(rm, cw, ld_cw, batch, e, ld_e, (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "polar rate match launch");
+}
+
+extern "C" int pl_polar_rate_recover(const pl_polar_rm* in, const void* llr, int64_t ld_llr, int64_t batch, double* out,
+                                     int64_t ld_out, double known_llr, int32_t flags, void* stream) {
+    pl_polar_rm rm;
+    if (int rc = polar_rate_match_args(in, &rm, llr, out, batch)) return rc;
+    if (flags & ~(PL_PRM_LLR_F32 | PL_PRM_ACCUMULATE)) return fail(PL_EINVAL, "unknown flag bits");
+    if (!(known_llr > 0.0) || !std::isfinite(known_llr)) return fail(PL_EINVAL, "known_llr must be finite and > 0");
+    if (((uintptr_t)llr & ((flags & PL_PRM_LLR_F32) ? 3 : 7)) || ((uintptr_t)out & 7))
+        return fail(PL_EINVAL, "llr_dev and out_dev must be aligned to their element type");
+    if (ld_llr < rm.E) return fail(PL_EINVAL, "ld_llr < E = " + std::to_string(rm.E));
+    if (ld_out < rm.N) return fail(PL_EINVAL, "ld_out < N = " + std::to_string(rm.N));
+    const hipError_t err = pl::polar_rate_recover_launch(rm, llr, ld_llr, flags & PL_PRM_LLR_F32, batch, out, ld_out,
+                                                         known_llr, flags & PL_PRM_ACCUMULATE, (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "polar rate recover launch");
+}
+
 extern "C" int pl_count_errors(const uint8_t* ref, int64_t ldr, const uint8_t* dec, int64_t ldd, int32_t width,
                                int64_t batch, int64_t* counts, void* stream) {
     if (batch < 0 || width < 0 || !counts || (batch > 0 && (!ref || !dec))) return fail(PL_EINVAL, "bad argument");

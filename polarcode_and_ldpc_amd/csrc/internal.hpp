@@ -169,4 +169,12 @@ hipError_t rate_recover_launch(const pl_rate_match& rm, const void* llr, int64_t
                                void* out, int64_t ldo, bool out_f32, int n_out, double filler, bool acc,
                                hipStream_t s);
 
+// ---- rate matching of polar codes (polar_ratematch.hip); pl_polar_rm: include/polarldpc.h ----
+// rm: checked (pl_polar_rate_match_check).  cw uint8 [batch][ldc], e uint8 [batch][lde]; llr [batch][ldl] float
+// or double, out double [batch][ldo], pitches in elements.  Both chunk their launches themselves.
+hipError_t polar_rate_match_launch(const pl_polar_rm& rm, const uint8_t* cw, int64_t ldc, int64_t batch, uint8_t* e,
+                                   int64_t lde, hipStream_t s);
+hipError_t polar_rate_recover_launch(const pl_polar_rm& rm, const void* llr, int64_t ldl, bool llr_f32, int64_t batch,
+                                     double* out, int64_t ldo, double known, bool acc, hipStream_t s);
+
 }  // namespace pl

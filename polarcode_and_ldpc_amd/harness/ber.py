@@ -50,25 +50,41 @@ def _log(log_path, mc, **key):
 
 def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: int, config: Dict,
                    list_size: int = 0, crc_polynomial: Optional[str] = None, batch: int = 65536, seed: int = 0,
-                   group=None, log_path=None):
+                   group=None, log_path=None, rate_match=None):
     """ber_simulation.py:132-198 -> (ber, fer, points).  list_size 0 = SC (the
     reference), >= 1 = SCL, with crc_polynomial = CA-SCL (CRC inside the K bits).
-    log_path: JSON-lines file of finished points; a rerun resumes from it."""
+    log_path: JSON-lines file of finished points; a rerun resumes from it.
+
+    rate_match: None, or a dict of PolarRateMatcher's arguments behind N (E, mode,
+    sub_blocks, known_llr): E bits of each frame are transmitted
+    (polar_round_fn's rate_matcher) and snr_db is per transmitted symbol.  The
+    frozen set is config["frozen_bits"] when present, else
+    construct_rate_matched(K, matcher) at its default design SNR.  E, mode, the
+    permutation and known_llr enter the log's run key only when rate matching is
+    used."""
     import torch
     from ..lib_wrappers import PolarLibWrapper
     from ..polar.decoder import CASCLDecoder, SCDecoder, SCLDecoder
     N, K = config["encoding"]["N"], config["encoding"]["K"]
-    fr = PolarLibWrapper(N, K, 2.0).get_frozen_bits_positions()
+    rm, more = None, {}
+    if rate_match is not None:
+        from ..polar.construction import construct_rate_matched
+        from ..polar.ratematch import PolarRateMatcher
+        rm = PolarRateMatcher(N, **rate_match)
+        fr = config["frozen_bits"] if "frozen_bits" in config else construct_rate_matched(K, rm)
+        more = dict(E=rm.E, mode=rm.mode, perm=rm.perm.tolist(), known_llr=rm.known_llr)
+    else:
+        fr = PolarLibWrapper(N, K, 2.0).get_frozen_bits_positions()
     if list_size <= 0:
         dec = SCDecoder(N, K, frozen_bits=fr)
     elif crc_polynomial:
         dec = CASCLDecoder(N, K, list_size, frozen_bits=fr, crc_polynomial=crc_polynomial)
     else:
         dec = SCLDecoder(N, K, list_size, frozen_bits=fr)
-    mc = MonteCarlo(polar_round_fn(dec, seed=seed, crc_polynomial=crc_polynomial), info_bits=K, batch=batch,
-                    group=group, device=torch.device("cuda", torch.cuda.current_device()))
+    mc = MonteCarlo(polar_round_fn(dec, seed=seed, crc_polynomial=crc_polynomial, rate_matcher=rm), info_bits=K,
+                    batch=batch, group=group, device=torch.device("cuda", torch.cuda.current_device()))
     log = _log(log_path, mc, code="polar", N=N, K=K, list_size=list_size, crc=crc_polynomial, frames=num_frames,
-               max_errors=max_errors, seed=seed, frozen=_digest(np.sort(np.asarray(fr))))
+               max_errors=max_errors, seed=seed, frozen=_digest(np.sort(np.asarray(fr))), **more)
     pts = mc.run(snr_db_range, num_frames, max_errors, log=log)
     return np.array([p.ber for p in pts]), np.array([p.fer for p in pts]), pts
 
@@ -220,6 +236,9 @@ def main(argv=None):
     ap.add_argument("--rm", default=None,
                     help="--code qcldpc: E,punctured,fillers[,ncb[,start]], rate matching (ldpc.QCRateMatcher): E bits "
                          "of each frame are transmitted")
+    ap.add_argument("--polar-rm", default=None,
+                    help="--code polar: E,mode[,p0,p1,...], rate matching (polar.PolarRateMatcher): E bits of each "
+                         "frame are transmitted; mode puncture or shorten; p0,p1,... the sub-block permutation")
     ap.add_argument("--dtype", choices=["float64", "float32"], default="float64",
                     help="--code qcldpc: the decoder's state and arithmetic")
     ap.add_argument("--fixed", default=None,
@@ -248,8 +267,14 @@ def main(argv=None):
         pts = mc.run(snr, a.frames, a.max_errors, log=log)
         ber, fer = np.array([p.ber for p in pts]), np.array([p.fer for p in pts])
     elif a.code == "polar":
+        more = {}
+        if a.polar_rm is not None:
+            f = a.polar_rm.split(",")
+            if len(f) < 2 or f[1] not in ("puncture", "shorten"):
+                ap.error("--polar-rm takes E,mode[,p0,p1,...] with mode puncture or shorten")
+            more["rate_match"] = dict(E=int(f[0]), mode=f[1], sub_blocks=[int(x) for x in f[2:]] or None)
         ber, fer, pts = simulate_polar(snr, a.frames, a.max_errors, {"encoding": {"N": a.N, "K": a.K}},
-                                       a.list_size, a.crc, a.batch, log_path=a.log)
+                                       a.list_size, a.crc, a.batch, log_path=a.log, **more)
     elif a.code == "qcldpc":
         from ..ldpc.matrix import qc_encodable_base
         q = [int(x) for x in a.qc.split(",")]

@@ -211,11 +211,66 @@ def _stream_seed(seed: int, snr_index: int) -> int:
     return (int(seed) * 0x9E3779B97F4A7C15 + (snr_index + 1) * 0xBF58476D1CE4E5B9) & (2 ** 64 - 1)
 
 
-def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None):
+def _polar_messages(msg, s, offset, K, crc_polynomial):
+    """polar_round_fn's messages (its plain path stays as it was): random K bits; with crc_polynomial, data
+    bits + their CRC on the device (pl_crc_append)."""
+    from .. import _native
+    _native.random_bits(s, offset, msg)
+    if crc_polynomial is not None:
+        from ..polar.utils import CRC_POLYNOMIALS
+        name = crc_polynomial if crc_polynomial in CRC_POLYNOMIALS else "CRC-8"
+        L = int(name.split("-")[1])
+        _native.crc_append(msg, K - L, L, CRC_POLYNOMIALS[name])
+
+
+def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm):
+    """polar_round_fn's rate-matched chain; see there."""
+    import torch
+    from .. import _native
+    from ..channel.awgn import AWGNChannel
+    N, K, E = decoder.N, decoder._n_info, rm.E
+    assert decoder.N == rm.N, "the decoder and the rate matcher must share the mother code: N = %d" % rm.N
+    rm.check_frozen(decoder.frozen_bits)
+    bufs = {}
+
+    def fn(snr_index, snr_db, offset, nframes):
+        if bufs.get("B", 0) < nframes:
+            bufs.update(B=nframes, msg=torch.empty((nframes, K), dtype=torch.uint8, device="cuda"),
+                        cw=torch.empty((nframes, N), dtype=torch.uint8, device="cuda"),
+                        tx=torch.empty((nframes, E), dtype=torch.uint8, device="cuda"),
+                        rx=torch.empty((nframes, E), dtype=torch.float64, device="cuda"),
+                        llr=torch.empty((nframes, N), dtype=torch.float64, device="cuda"),
+                        out=torch.empty((nframes, K), dtype=torch.uint8, device="cuda"))
+        msg, cw, tx, rx, llr, out = (bufs[k][:nframes] for k in ("msg", "cw", "tx", "rx", "llr", "out"))
+        s = _stream_seed(seed, snr_index)
+        _polar_messages(msg, s, offset, K, crc_polynomial)
+        _native.polar_encode(decoder.plan, msg, cw)
+        rm.select(cw, out=tx)
+        AWGNChannel(snr_db).llr_batch_device(tx, E, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=rx)
+        rm.recover(rx, out=llr)
+        decoder.plan.decode(llr, out)
+        counts = torch.zeros(3, dtype=torch.int64, device="cuda")
+        _native.count_errors(msg, out, K, counts)
+        return counts.cpu().numpy()
+
+    return fn
+
+
+def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None, rate_matcher=None):
     """Round function for a drop-in SC/SCL decoder (polar.SCDecoder/SCLDecoder).
     Random K-bit messages (CRC appended when crc_polynomial is given, as
     src/polar/encoder.py:74-78 does), device polar encoder, device AWGN,
-    decode, device error count over the K decoded bits."""
+    decode, device error count over the K decoded bits.
+
+    rate_matcher = a polar.PolarRateMatcher of the decoder's N: only E bits of
+    each frame cross the channel.  Messages (+ CRC), pl_polar_encode, select,
+    AWGN over the E symbols (same seed derivation as without a matcher), recover
+    to N fp64 LLRs, decode, count.  snr_db is per transmitted symbol (Es/N0), as
+    in the LDPC chain: a repeated bit collects the energy of each copy.  The
+    decoder's frozen set must contain rate_matcher.forced_frozen()
+    (check_frozen; polar.construct_rate_matched builds one)."""
+    if rate_matcher is not None:
+        return _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rate_matcher)
     import torch
     from .. import _native
     from ..channel.awgn import AWGNChannel

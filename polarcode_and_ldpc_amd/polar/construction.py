@@ -93,3 +93,63 @@ def construct_frozen_set(N: int, K: int, snr_db: float = 2.0, bit_reversed: bool
     if bit_reversed:
         frozen = bit_reverse_indices(int(np.log2(N)))[frozen]
     return np.sort(np.asarray(frozen, dtype=np.int64))
+
+
+def bit_channel_bhattacharyya(z_leaf) -> np.ndarray:
+    """Bhattacharyya parameter of each u_l given one per codeword position (the leaves may differ), in the
+    decoders' order: the first f/g level pairs the adjacent inputs (x[2k], x[2k+1]) and the even-indexed
+    u are decoded from the f outputs (oracle/refnumpy.py:_llr_pass, stage 0 has half = 1).  So on
+    a = z[0::2], b = z[1::2]: out[0::2] = rec(a + b - a b), out[1::2] = rec(a b).  With equal leaves this
+    is bhattacharyya_bounds(N, snr)[bit_reverse_indices(n)] up to rounding."""
+    z = np.asarray(z_leaf, dtype=np.float64)
+    assert z.ndim == 1 and len(z) >= 1 and len(z) & (len(z) - 1) == 0, "one value per position, a power of 2 of them"
+    if len(z) == 1:
+        return z.copy()
+    a, b = z[0::2], z[1::2]
+    out = np.empty(len(z))
+    out[0::2] = bit_channel_bhattacharyya(a + b - a * b)
+    out[1::2] = bit_channel_bhattacharyya(a * b)
+    return out
+
+
+def construct_rate_matched(K: int, matcher, snr_db: float = 2.0) -> np.ndarray:
+    """Sorted frozen index set of a K-bit code on the rate-matched mother code of `matcher` (a
+    polar.PolarRateMatcher), for the SC/SCL decoders.
+
+    Leaf Z per codeword position, with Z0 = exp(-10^(snr_db / 10)) per transmitted symbol: a position
+    sent c times math.pow(Z0, c); punctured 1.0 (nothing is known); shortened 0.0 (known).  The bit
+    channels' Z come from bit_channel_bhattacharyya.  The information set is the first K of
+    np.argsort(Z, kind="stable") restricted to the indices outside matcher.forced_frozen(): ties go to
+    the lower index.
+
+    Example, exact in floating point: N = 8, E = 6, puncture, sub_blocks None, snr_db = 30, so that
+    Z0 = exp(-1000) = 0.0.  Positions 0 and 1 are punctured: the leaves are (1, 1, 0, 0, 0, 0, 0, 0).
+    The first level pairs (1, 1), (0, 0), (0, 0), (0, 0): the f side is (1 + 1 - 1, 0, 0, 0) = (1, 0, 0, 0)
+    and feeds the even u, the g side is (1 * 1, 0, 0, 0) = (1, 0, 0, 0) and feeds the odd u.  On either,
+    the next level pairs (1, 0) and (0, 0): f side (1, 0), g side (0, 0); and the last level turns (1, 0)
+    into (1, 0) and (0, 0) into (0, 0).  Interleaving back, Z = (1, 1, 0, 0, 0, 0, 0, 0) by index: u_0 and
+    u_1 carry nothing, and six indices tie at 0.0.  The stable order is 2, 3, 4, 5, 6, 7, 0, 1, so K = 3
+    gives the information set {2, 3, 4} and the frozen set {0, 1, 5, 6, 7}: ties go to the lower index.
+    K = 7 would take index 0 with Z = 1.0 and raises.
+
+    ValueError when fewer than K indices lie outside the forced set, or when a chosen index has
+    Z >= 1.0: too many information bits for what is sent at this design SNR, or rounding has hidden a
+    zero-capacity channel."""
+    N = matcher.N
+    z0 = math.exp(-(10 ** (snr_db / 10.0)))
+    count = np.bincount(matcher.positions_host(), minlength=N)
+    leaf = np.array([math.pow(z0, int(c)) if c else (0.0 if matcher.mode == "shorten" else 1.0) for c in count])
+    Z = bit_channel_bhattacharyya(leaf)
+    forced = np.zeros(N, dtype=bool)
+    forced[matcher.forced_frozen()] = True
+    order = [int(i) for i in np.argsort(Z, kind="stable") if not forced[i]]
+    if K < 1 or len(order) < K:
+        raise ValueError("K = %d outside 1 .. %d, the indices that shortening leaves free" % (K, len(order)))
+    info = order[:K]
+    worst = max(Z[i] for i in info)
+    if worst >= 1.0:
+        raise ValueError("K = %d puts information on a bit channel with Z >= 1: too many information bits for "
+                         "E = %d at the design SNR %g dB" % (K, matcher.E, snr_db))
+    frozen = np.ones(N, dtype=bool)
+    frozen[info] = False
+    return np.flatnonzero(frozen).astype(np.int64)
