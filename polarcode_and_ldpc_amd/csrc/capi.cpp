@@ -13,6 +13,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -451,7 +452,7 @@ extern "C" int pl_ldpc_qc_fixed_plan_create(int32_t mb, int32_t nb, int32_t z, c
     p->qfg = hp.geom;
     p->lg.n = p->lms.n = hp.geom.n;
     p->lg.m = p->lms.m = hp.geom.m;
-    const hipError_t e = pl::qc_fixed_prepare(p->qfg);
+    const hipError_t e = pl::qc_prepare(p->qfg);
     if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute");
     p->ws_unit = p->qfg.use_global ? (size_t)p->qfg.state_bytes : 0;
     *out = plan.release();
@@ -575,13 +576,17 @@ struct DecodeDiag {
 
 // Layered min-sum decode; post ([batch][ld_post]) may be null.  LDS-resident
 // state: launches below the grid limit; workspace-resident: chunks of the frames
-// the workspace holds (one state slice per frame of a chunk).  IO: double, or
-// float on a quasi-cyclic plan made with PL_LDPC_QC_F32 (pl_ldpc_decode_f32 checks that).
+// the workspace holds (one state slice per frame of a chunk).  IO: double; float on a
+// quasi-cyclic plan made with PL_LDPC_QC_F32; int8_t on a fixed-point plan (pl_ldpc_decode_f32
+// and pl_ldpc_decode_i8 check that).
 template <typename IO>
 static int lms_decode_impl(pl_plan* p, const IO* llr, int64_t batch, int64_t ld, uint8_t* bits, int32_t* iters,
                            IO* post, int64_t ld_post, void* ws, size_t ws_bytes, hipStream_t s) {
+    constexpr bool kFixed = std::is_same<IO, int8_t>::value;
     if (p->ws_unit > 0 && (ws == nullptr || ws_bytes < p->ws_unit))
         return fail(PL_EINVAL, "workspace smaller than one unit (pl_plan_workspace_bytes)");
+    if (kFixed && p->ws_unit > 0 && ((uintptr_t)ws & 15))
+        return fail(PL_EINVAL, "workspace must be aligned to 16 bytes");
     const int64_t step = p->ws_unit > 0 ? std::min<int64_t>(p->ldpc_chunk, (int64_t)(ws_bytes / p->ws_unit))
                                         : kMaxLaunchItems / 1024;
     return for_chunks(batch, step, [&](int64_t b0, int64_t nb) {
@@ -589,15 +594,18 @@ static int lms_decode_impl(pl_plan* p, const IO* llr, int64_t batch, int64_t ld,
         int32_t* const io = iters ? iters + b0 : nullptr;
         IO* const po = post ? post + b0 * ld_post : nullptr;
         hipError_t e;
-        if constexpr (sizeof(IO) == sizeof(double)) {
+        if constexpr (kFixed) {
+            e = pl::qc_launch(p->qfg, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb, (unsigned char*)ws, s);
+        } else if constexpr (std::is_same<IO, float>::value) {
+            e = pl::qc_launch(p->qcg, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb, (unsigned char*)ws, s);
+        } else {
             e = p->qc ? pl::qc_launch(p->qcg, p->qc_f32, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
                                       (unsigned char*)ws, s)
                       : pl::lms_launch(p->lms, p->lmsd, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
                                        (unsigned char*)ws, s);
-        } else {
-            e = pl::qc_launch(p->qcg, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb, (unsigned char*)ws, s);
         }
-        return e == hipSuccess ? PL_OK : hipfail(e, "layered ldpc decode launch");
+        if (e == hipSuccess) return PL_OK;
+        return hipfail(e, kFixed ? "fixed-point ldpc decode launch" : "layered ldpc decode launch");
     });
 }
 
@@ -871,20 +879,17 @@ extern "C" int pl_ldpc_decode_soft(pl_plan* p, const double* llr, int64_t batch,
     });
 }
 
-extern "C" int pl_ldpc_decode_f32(pl_plan* p, const float* llr, int64_t batch, int64_t ld, uint8_t* bits,
-                                  int32_t* iters, float* post, int64_t ld_post, void* workspace,
-                                  int64_t workspace_bytes, void* stream) {
-    if (!p) return fail(PL_EINVAL, "plan is NULL");
-    if (p->qc_fixed) return fail(PL_EUNSUPPORTED, kFixedOnly);
-    if (!p->qc || !p->qc_f32)
-        return fail(PL_EUNSUPPORTED, "fp32 LLRs: quasi-cyclic plans created with PL_LDPC_QC_F32 only");
-    int rc = check_decode_args(p, batch, ld, llr, bits);
+// pl_ldpc_decode_f32's and pl_ldpc_decode_i8's part behind their refusals by the plan's kind: on the
+// caller's workspace, or with a null one on the stream's
+template <typename IO>
+static int lms_decode_typed(pl_plan* p, const IO* llr, int64_t batch, int64_t ld, uint8_t* bits, int32_t* iters,
+                            IO* post, int64_t ld_post, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    int rc = check_decode_args(p, batch, ld, llr, bits, std::is_same<IO, int8_t>::value);
     if (rc) return rc;
     if (post && ld_post < p->lms.n) return fail(PL_EINVAL, "ld_post < n");
     if (workspace && workspace_bytes < 0) return fail(PL_EINVAL, "workspace_bytes < 0");
     if (batch == 0) return PL_OK;
     if ((rc = check_device(p))) return rc;
-    const hipStream_t s = (hipStream_t)stream;
     if (workspace)
         return lms_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, workspace, (size_t)workspace_bytes, s);
     return with_stream_ws(p, s, ws_need(p, batch), [&](void* ws, size_t bytes) {
@@ -892,21 +897,15 @@ extern "C" int pl_ldpc_decode_f32(pl_plan* p, const float* llr, int64_t batch, i
     });
 }
 
-// pl_ldpc_decode_i8's launches: lms_decode_impl's chunking on the fixed-point kernel
-static int fixed_decode_impl(pl_plan* p, const int8_t* llr, int64_t batch, int64_t ld, uint8_t* bits, int32_t* iters,
-                             int8_t* post, int64_t ld_post, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (p->ws_unit > 0 && (ws == nullptr || ws_bytes < p->ws_unit))
-        return fail(PL_EINVAL, "workspace smaller than one unit (pl_plan_workspace_bytes)");
-    if (p->ws_unit > 0 && ((uintptr_t)ws & 15))
-        return fail(PL_EINVAL, "workspace must be aligned to 16 bytes");
-    const int64_t step = p->ws_unit > 0 ? std::min<int64_t>(p->ldpc_chunk, (int64_t)(ws_bytes / p->ws_unit))
-                                        : kMaxLaunchItems / 1024;
-    return for_chunks(batch, step, [&](int64_t b0, int64_t nb) {
-        const hipError_t e = pl::qc_fixed_launch(p->qfg, p->d_ldpc, llr + b0 * ld, ld, bits + b0 * p->lms.n,
-                                                 iters ? iters + b0 : nullptr, post ? post + b0 * ld_post : nullptr,
-                                                 ld_post, nb, (unsigned char*)ws, s);
-        return e == hipSuccess ? PL_OK : hipfail(e, "fixed-point ldpc decode launch");
-    });
+extern "C" int pl_ldpc_decode_f32(pl_plan* p, const float* llr, int64_t batch, int64_t ld, uint8_t* bits,
+                                  int32_t* iters, float* post, int64_t ld_post, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+    if (!p) return fail(PL_EINVAL, "plan is NULL");
+    if (p->qc_fixed) return fail(PL_EUNSUPPORTED, kFixedOnly);
+    if (!p->qc || !p->qc_f32)
+        return fail(PL_EUNSUPPORTED, "fp32 LLRs: quasi-cyclic plans created with PL_LDPC_QC_F32 only");
+    return lms_decode_typed(p, llr, batch, ld, bits, iters, post, ld_post, workspace, workspace_bytes,
+                            (hipStream_t)stream);
 }
 
 extern "C" int pl_ldpc_decode_i8(pl_plan* p, const int8_t* llr, int64_t batch, int64_t ld, uint8_t* bits,
@@ -915,18 +914,8 @@ extern "C" int pl_ldpc_decode_i8(pl_plan* p, const int8_t* llr, int64_t batch, i
     if (!p) return fail(PL_EINVAL, "plan is NULL");
     if (!p->qc_fixed)
         return fail(PL_EUNSUPPORTED, "int8 LLRs: fixed-point plans (pl_ldpc_qc_fixed_plan_create) only");
-    int rc = check_decode_args(p, batch, ld, llr, bits, true);
-    if (rc) return rc;
-    if (post && ld_post < p->lms.n) return fail(PL_EINVAL, "ld_post < n");
-    if (workspace && workspace_bytes < 0) return fail(PL_EINVAL, "workspace_bytes < 0");
-    if (batch == 0) return PL_OK;
-    if ((rc = check_device(p))) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (workspace)
-        return fixed_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, workspace, (size_t)workspace_bytes, s);
-    return with_stream_ws(p, s, ws_need(p, batch), [&](void* ws, size_t bytes) {
-        return fixed_decode_impl(p, llr, batch, ld, bits, iters, post, ld_post, ws, bytes, s);
-    });
+    return lms_decode_typed(p, llr, batch, ld, bits, iters, post, ld_post, workspace, workspace_bytes,
+                            (hipStream_t)stream);
 }
 
 extern "C" int pl_llr_quantize(const void* llr, int32_t flags, int64_t ld, int64_t batch, int32_t n, double scale,
@@ -1086,14 +1075,14 @@ extern "C" int pl_plan_get_info(const pl_plan* p, pl_plan_info* info) {
         info->kind = 1; info->n_in = p->lms.n; info->n_out = p->lms.n; info->list_size = 0;
         info->lds_bytes = p->lms.lds_bytes; info->fused_top = 0; info->frames_per_block = p->lms.fpb;
         info->reserved = pl::lms_kernel_code(p->lms);  // layered min-sum: 9 state in LDS, 10 in the workspace
-        if (p->qc) {  // quasi-cyclic layered min-sum: 11 state in LDS, 12 in the workspace; fp32 state: 13, 14
-            info->lds_bytes = p->qcg.lds_bytes; info->frames_per_block = p->qcg.fpw * p->qcg.fpb;
-            info->reserved = pl::qc_kernel_code(p->qcg, p->qc_f32);
-        }
-        if (p->qc_fixed) {  // int8 fixed-point quasi-cyclic layered min-sum: 15 state in LDS, 16 in the workspace
-            info->lds_bytes = p->qfg.lds_bytes; info->frames_per_block = p->qfg.fpw * p->qfg.fpb;
-            info->fused_top = p->qfg.dcap;  // the instance: inputs of a check kept in registers, 0 the two-pass form
-            info->reserved = pl::qc_fixed_kernel_code(p->qfg);
+        if (p->qc || p->qc_fixed) {
+            const pl::QcMap& q = p->qc ? static_cast<const pl::QcMap&>(p->qcg) : p->qfg;
+            info->lds_bytes = q.lds_bytes; info->frames_per_block = q.fpw * q.fpb;
+            // quasi-cyclic layered min-sum: 11 state in LDS, 12 in the workspace; fp32 state: 13, 14; int8
+            // fixed point: 15, 16
+            info->reserved = p->qc ? pl::qc_kernel_code(p->qcg, p->qc_f32) : pl::qc_fixed_kernel_code(p->qfg);
+            // the fixed-point instance: inputs of a check kept in registers, 0 the two-pass form
+            if (p->qc_fixed) info->fused_top = q.dcap;
         }
     } else {
         info->kind = 1; info->n_in = p->lg.n; info->n_out = p->lg.n; info->list_size = 0;

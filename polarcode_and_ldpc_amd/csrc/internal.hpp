@@ -134,8 +134,10 @@ hipError_t lms_prepare(const LmsGeom& g);
 hipError_t lms_launch(const LmsGeom& g, const LmsDev& d, const double* llr, int64_t ld, uint8_t* bits, int32_t* iters,
                       double* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
 
-// ---- quasi-cyclic layered min-sum (ldpc_qc_layered.hip); QcGeom: ldpc_plan.hpp ----
-// f32: a single-precision plan (QcHostPlan::f32): the float instances, which take fp64 or fp32 llr / post
+// ---- quasi-cyclic layered min-sum: one overload set over the geometry and the type of llr / post; the
+// kernel behind all of them is ldpc_qc_frame.hpp's.  QcGeom, QcFixedGeom: ldpc_plan.hpp ----
+// floating point (ldpc_qc_layered.hip).  f32: a single-precision plan (QcHostPlan::f32): the float
+// instances, which take fp64 or fp32 llr / post
 hipError_t qc_prepare(const QcGeom& g, bool f32);
 // tab: the plan's layer stream (device); the other arguments as lms_launch
 hipError_t qc_launch(const QcGeom& g, bool f32, const int32_t* tab, const double* llr, int64_t ld, uint8_t* bits,
@@ -144,12 +146,12 @@ hipError_t qc_launch(const QcGeom& g, bool f32, const int32_t* tab, const double
 hipError_t qc_launch(const QcGeom& g, const int32_t* tab, const float* llr, int64_t ld, uint8_t* bits, int32_t* iters,
                      float* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
 
-// ---- int8 fixed-point quasi-cyclic layered min-sum and the LLR quantiser (ldpc_qc_fixed.hip) ----
-hipError_t qc_fixed_prepare(const QcFixedGeom& g);
-// llr int8 [batch][ld]; post int8 [batch][ld_post] or null; the other arguments as qc_launch
-hipError_t qc_fixed_launch(const QcFixedGeom& g, const int32_t* tab, const int8_t* llr, int64_t ld, uint8_t* bits,
-                           int32_t* iters, int8_t* post, int64_t ld_post, int64_t batch, unsigned char* work,
-                           hipStream_t s);
+// int8 fixed point (ldpc_qc_fixed.hip): llr int8 [batch][ld]; post int8 [batch][ld_post] or null
+hipError_t qc_prepare(const QcFixedGeom& g);
+hipError_t qc_launch(const QcFixedGeom& g, const int32_t* tab, const int8_t* llr, int64_t ld, uint8_t* bits,
+                     int32_t* iters, int8_t* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
+
+// ---- the LLR quantiser (ldpc_qc_fixed.hip) ----
 // llr [batch][ldi] double, or float with f32; out int8 [batch][ldo]; chunks its launches itself
 hipError_t llr_quantize_launch(const void* llr, bool f32, int64_t ldi, int64_t batch, int n, double scale, int llr_max,
                                int8_t* out, int64_t ldo, hipStream_t s);

@@ -499,12 +499,15 @@ static PlanStatus qc_check_and_stream(int mb, int nb, int z, const int32_t* shif
     return {};
 }
 
-// Frames to lanes and the state's home, from g.z and g.state_bytes (QcGeom and QcFixedGeom name the
-// fields alike): the 160 KB bound on a workgroup's LDS and, for z <= 64, the 64 KB a wavefront's frames
-// may take before fewer than four wavefronts share a workgroup.
-template <class G>
-static void qc_map(G& g, bool force_global) {
+// The shared part of a quasi-cyclic plan's geometry: the code, the instance (dcap), and from z and
+// state_bytes the frames' lanes and the state's home: the 160 KB bound on a workgroup's LDS and, for
+// z <= 64, the 64 KB a wavefront's frames may take before fewer than four wavefronts share a workgroup.
+static void qc_map(QcMap& g, int mb, int nb, int z, int max_iter, int early_stop, int maxdc, int mw,
+                   int64_t state_bytes, bool force_global) {
     constexpr int kLdsMax = 160 * 1024;
+    g.mb = mb; g.nb = nb; g.z = z; g.m = mb * z; g.n = nb * z; g.max_iter = max_iter; g.early_stop = early_stop ? 1 : 0;
+    g.maxdc = maxdc; g.mw = mw; g.state_bytes = state_bytes;
+    g.dcap = maxdc <= 8 ? 8 : maxdc <= 16 ? 16 : maxdc <= kQcDcapMax ? 32 : 0;
     g.subwave = g.z <= 64 ? 1 : 0;
     if (g.subwave) {
         // fpw frames side by side in a wavefront's lanes; the LDS bound of lms_geom's WAVE case, per wavefront
@@ -534,19 +537,16 @@ PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int3
     lms_geom(&lg, opt.lms_global);
     QcGeom& g = out->geom;
     g = QcGeom{};
-    out->f32 = false;
-    g.mb = mb; g.nb = nb; g.z = z; g.m = lg.m; g.n = lg.n; g.max_iter = max_iter; g.early_stop = early_stop ? 1 : 0;
-    g.maxdc = maxdc; g.norm = norm; g.mw = lg.mw;
-    g.dcap = maxdc <= 8 ? 8 : maxdc <= 16 ? 16 : maxdc <= kQcDcapMax ? 32 : 0;
-    g.state_bytes = lg.state_bytes; g.off_mm = lg.off_mm; g.off_meta = lg.off_meta;
-    if (opt.qc_state_elem == 4) {  // the same arrays with 4-byte P and minima; the rules below see the new sizes
-        out->f32 = true;
+    out->f32 = opt.qc_state_elem == 4;
+    g.norm = norm; g.off_mm = lg.off_mm; g.off_meta = lg.off_meta;
+    int64_t state_bytes = lg.state_bytes;
+    if (out->f32) {  // the same arrays with 4-byte P and minima
         g.norm = (double)(float)norm;  // rounded once, here; the kernel's (float)g.norm is exact
-        g.off_mm = (int64_t)ldpc_align16((size_t)4 * g.n);
-        g.off_meta = g.off_mm + (int64_t)8 * g.m;
-        g.state_bytes = (int64_t)ldpc_align16((size_t)g.off_meta + (size_t)4 * g.m * g.mw);
+        g.off_mm = (int64_t)ldpc_align16((size_t)4 * lg.n);
+        g.off_meta = g.off_mm + (int64_t)8 * lg.m;
+        state_bytes = (int64_t)ldpc_align16((size_t)g.off_meta + (size_t)4 * lg.m * lg.mw);
     }
-    qc_map(g, opt.lms_global);
+    qc_map(g, mb, nb, z, max_iter, early_stop, maxdc, lg.mw, state_bytes, opt.lms_global);
     return {};
 }
 
@@ -559,13 +559,11 @@ PlanStatus qc_fixed_plan_build(int mb, int nb, int z, const int32_t* shift, cons
     if (st.code) return st;
     QcFixedGeom& g = out->geom;
     g = QcFixedGeom{};
-    g.mb = mb; g.nb = nb; g.z = z; g.m = mb * z; g.n = nb * z; g.max_iter = max_iter; g.early_stop = early_stop ? 1 : 0;
-    g.maxdc = maxdc; g.norm16 = norm16; g.llr_max = llr_max; g.msg_max = msg_max;
-    g.dcap = maxdc <= 8 ? 8 : maxdc <= 16 ? 16 : maxdc <= kQcDcapMax ? 32 : 0;
-    g.mw = maxdc <= kQcFixedOneWord ? 1 : 1 + (maxdc + 31) / 32;
-    g.off_p = (int64_t)4 * g.m * g.mw;
-    g.state_bytes = (int64_t)ldpc_align16((size_t)g.off_p + (size_t)g.n);
-    qc_map(g, opt.lms_global);
+    g.norm16 = norm16; g.llr_max = llr_max; g.msg_max = msg_max;
+    const int mw = maxdc <= kQcFixedOneWord ? 1 : 1 + (maxdc + 31) / 32;
+    g.off_p = (int64_t)4 * (mb * z) * mw;
+    const int64_t state_bytes = (int64_t)ldpc_align16((size_t)g.off_p + (size_t)(nb * z));
+    qc_map(g, mb, nb, z, max_iter, early_stop, maxdc, mw, state_bytes, opt.lms_global);
     return {};
 }
 

@@ -193,29 +193,36 @@ PlanStatus lms_plan_build(int m, int n, const int32_t* row_ptr, const int32_t* c
                           const int32_t* layer_ptr, const int32_t* layer_rows, int max_iter, int early_stop,
                           double norm, const LdpcPlanOptions& opt, LmsHostPlan* out);
 
-// ---- quasi-cyclic layered min-sum (ldpc_qc_layered.hip) ----
+// ---- quasi-cyclic layered min-sum: the code and its mapping (ldpc_qc_frame.hpp) ----
 // H is mb x nb blocks of z x z, each zero or a cyclically shifted identity; a
-// block row is a layer.  State layout per frame: lms_geom's; with f32 the same
-// arrays in single precision: P[n] f32, at off_mm = align16(4 n) [m] float2, at
-// off_meta = off_mm + 8 m the same [m][mw] u32, state_bytes = align16(off_meta + 4 m mw).
-struct QcGeom {
+// block row is a layer.  What qc_frame_kernel reads whatever the arithmetic; the
+// geometry of a decoder is this and its own state layout.
+struct QcMap {
     int mb, nb, z, m, n, max_iter, early_stop, maxdc;
-    double norm;     // a single-precision plan: (float)normalization, rounded by the planner (exact as a float)
-    int mw;          // meta words per check, as LmsGeom::mw
+    int64_t state_bytes;  // per frame
+    int mw;          // u32 words of a check's state next to its minima (QcGeom) or in all (QcFixedGeom)
     int dcap;        // inputs of a check kept in registers: 8, 16 or 32 (>= maxdc); 0: two-pass form
     int subwave;     // 1 (z <= 64): fpw frames share a wavefront; 0: one workgroup per frame
     int use_global;  // state in the workspace instead of LDS
     int fpw;         // frames per wavefront (64 / z; 1 when !subwave)
     int fpb;         // wavefronts per workgroup when subwave, else 1: a workgroup decodes fpw fpb frames
     int threads, lds_bytes;
-    int64_t state_bytes, off_mm, off_meta;
 };
 constexpr int kQcMaxZ = 1024;
-constexpr int kQcDcapMax = 32;  // largest register-resident instance of ldpc_qc_kernel
+constexpr int kQcDcapMax = 32;  // largest register-resident instance of qc_frame_kernel
+
+// ---- floating-point quasi-cyclic layered min-sum (ldpc_qc_layered.hip) ----
+// State layout per frame: lms_geom's (mw meta words per check, as LmsGeom::mw); with f32 the same
+// arrays in single precision: P[n] f32, at off_mm = align16(4 n) [m] float2, at
+// off_meta = off_mm + 8 m the same [m][mw] u32, state_bytes = align16(off_meta + 4 m mw).
+struct QcGeom : QcMap {
+    double norm;  // a single-precision plan: (float)normalization, rounded by the planner (exact as a float)
+    int64_t off_mm, off_meta;
+};
 inline int qc_kernel_code(const QcGeom& g, bool f32 = false) { return (g.use_global ? 12 : 11) + (f32 ? 2 : 0); }
 struct QcHostPlan {
     QcGeom geom{};
-    bool f32 = false;  // state and arithmetic in binary32: the float instances of ldpc_qc_kernel
+    bool f32 = false;  // state and arithmetic in binary32: the float instances of qc_frame_kernel
     // per layer, in layer order: block row, its degree d, then d (block column, shift) pairs by
     // ascending block column -- a stream the kernel walks front to back, 2 + 2 d words a layer
     std::vector<int32_t> tables;
@@ -236,13 +243,9 @@ PlanStatus qc_plan_build(int mb, int nb, int z, const int32_t* shift, const int3
 //               the parity bit 27; words 1 ..: the negative flags, position j at bit j % 32 of word 1 + j / 32
 //   at off_p = 4 m mw   P[n] int8
 //   state_bytes = align16(off_p + n): n + 4 m rounded up to 16 for degrees <= 14, n + 8 m up to 32.
-struct QcFixedGeom {
-    int mb, nb, z, m, n, max_iter, early_stop, maxdc;
+struct QcFixedGeom : QcMap {       // mw: 1 (maxdc <= kQcFixedOneWord) or 1 + ceil(maxdc / 32)
     int norm16, llr_max, msg_max;  // the normalisation in sixteenths and the two saturation bounds
-    int mw;          // u32 words per check: 1 (maxdc <= kQcFixedOneWord) or 1 + ceil(maxdc / 32)
-    int dcap;        // as QcGeom::dcap
-    int subwave, use_global, fpw, fpb, threads, lds_bytes;  // as QcGeom's
-    int64_t state_bytes, off_p;
+    int64_t off_p;
 };
 constexpr int kQcFixedOneWord = 14;  // 7 + 7 bits of minima, 4 of idx1 and 14 flags fill a word
 inline int qc_fixed_kernel_code(const QcFixedGeom& g) { return g.use_global ? 16 : 15; }

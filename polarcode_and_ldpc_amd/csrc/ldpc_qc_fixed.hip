@@ -4,13 +4,9 @@
 // include/polarldpc.h, pl_ldpc_qc_fixed_plan_create and pl_llr_quantize.  All
 // arithmetic is on 32-bit integers in registers, |values| <= 254; only the
 // state is narrow.
-// Mapping: ldpc_qc_kernel's (ldpc_qc_layered.hip) -- one thread per check of the
-// current block row; SUBWAVE (Z <= 64): 64 / Z frames per wavefront, no workgroup
-// barrier, each frame stops on its own zero syndrome by ballot; otherwise one
-// workgroup per frame; DCAP > 0: the q_j of a check stay in registers between
-// the two passes, DCAP == 0: the two-pass form.  The layer stream is the same.
-// State per frame (ldpc_plan.hpp, QcFixedGeom), in LDS or (GLOBAL) in the frame's
-// workspace slice:
+// The kernel, its mapping and its synchronisation: ldpc_qc_frame.hpp; this file
+// is its int8 rule.
+// State per frame (ldpc_plan.hpp, QcFixedGeom):
 //   at 0      [m][mw] u32 per check.  maxdc <= 14 (the DCAP 8 instances, and the DCAP
 //             16 ones when the plan says so), mw = 1: the two minima already scaled
 //             and clamped (bits 0-6, 7-13), idx1 (14-17), the negative flags
@@ -22,16 +18,10 @@
 //   at off_p  P[n] int8
 // The checks of a block row touch distinct variables, and LDS and global byte
 // stores write their byte only, so neighbouring lanes may share a dword of P.
-#include "common.hpp"
-#include "internal.hpp"
-#include "ldpc_lms_check.hpp"  // lms_sync, lms_wg_any
+#include "ldpc_qc_frame.hpp"
 
 namespace pl {
 
-PL_DEV int qf_var(int col, int s, int r, int z) {
-    const int t = r + s;
-    return col * z + (t >= z ? t - z : t);
-}
 PL_DEV int qf_clamp(int x, int lim) { return x < -lim ? -lim : (x > lim ? lim : x); }
 
 struct QfCheck {
@@ -90,7 +80,7 @@ PL_DEV void qf_check_update(const QcFixedGeom& g, const int32_t* __restrict__ pr
         for (int j = 0; j < DCAP; ++j) {
             q[j] = 0;
             if (j < d) {
-                const int p = P[qf_var(pr[2 * j], pr[2 * j + 1], r, g.z)];
+                const int p = P[qc_var(pr[2 * j], pr[2 * j + 1], r, g.z)];
                 q[j] = qf_clamp(p - qf_c2v(old, (negw >> j) & 1u, (uint32_t)j), 127);
                 mn.take(q[j], (uint32_t)j);
             }
@@ -101,7 +91,7 @@ PL_DEV void qf_check_update(const QcFixedGeom& g, const int32_t* __restrict__ pr
         for (int j = 0; j < DCAP; ++j) {
             if (j < d) {
                 const uint32_t nb = q[j] < 0 ? 1u : 0u;
-                P[qf_var(pr[2 * j], pr[2 * j + 1], r, g.z)] = (int8_t)qf_clamp(q[j] + qf_c2v(nw, nb, (uint32_t)j), 127);
+                P[qc_var(pr[2 * j], pr[2 * j + 1], r, g.z)] = (int8_t)qf_clamp(q[j] + qf_c2v(nw, nb, (uint32_t)j), 127);
                 acc |= nb << j;
             }
         }
@@ -115,7 +105,7 @@ PL_DEV void qf_check_update(const QcFixedGeom& g, const int32_t* __restrict__ pr
         uint32_t negw = 0;
         for (int j = 0; j < d; ++j) {
             if (!first && (j & 31) == 0) negw = cw[1 + (j >> 5)];
-            const int p = P[qf_var(pr[2 * j], pr[2 * j + 1], r, g.z)];
+            const int p = P[qc_var(pr[2 * j], pr[2 * j + 1], r, g.z)];
             mn.take(qf_clamp(p - qf_c2v(old, (negw >> (j & 31)) & 1u, (uint32_t)j), 127), (uint32_t)j);
         }
         const QfCheck nw = mn.scaled(g);
@@ -123,7 +113,7 @@ PL_DEV void qf_check_update(const QcFixedGeom& g, const int32_t* __restrict__ pr
         negw = 0;
         for (int j = 0; j < d; ++j) {
             if (!first && (j & 31) == 0) negw = cw[1 + (j >> 5)];  // the old flags: this word is stored below, after its last use
-            const int v = qf_var(pr[2 * j], pr[2 * j + 1], r, g.z);
+            const int v = qc_var(pr[2 * j], pr[2 * j + 1], r, g.z);
             const int q = qf_clamp((int)P[v] - qf_c2v(old, (negw >> (j & 31)) & 1u, (uint32_t)j), 127);
             const uint32_t nb = q < 0 ? 1u : 0u;
             P[v] = (int8_t)qf_clamp(q + qf_c2v(nw, nb, (uint32_t)j), 127);
@@ -134,126 +124,26 @@ PL_DEV void qf_check_update(const QcFixedGeom& g, const int32_t* __restrict__ pr
     }
 }
 
-template <int DCAP, bool SUBWAVE, bool GLOBAL>
-__global__ void __launch_bounds__(SUBWAVE ? 256 : 1024)
-ldpc_qc_fixed_kernel(QcFixedGeom g, const int32_t* __restrict__ tab, const int8_t* __restrict__ llr, int64_t ld,
-                     uint8_t* __restrict__ bits, int32_t* __restrict__ iters, int8_t* __restrict__ post,
-                     int64_t ld_post, int64_t batch, unsigned char* __restrict__ work) {
-    extern __shared__ __align__(16) unsigned char qf_smem[];
-    const int z = g.z;
-    int r, f = 0, slot = 0;
-    int64_t frame;
-    bool mine;  // this lane holds check r of a frame of the batch
-    if (SUBWAVE) {
-        const int wv = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
-        const int64_t wave0 = ((int64_t)blockIdx.x * g.fpb + wv) * g.fpw;
-        if (wave0 >= batch) return;  // a ragged last workgroup (no workgroup barrier below)
-        f = lane / z;
-        r = lane - f * z;
-        frame = wave0 + f;
-        mine = f < g.fpw && frame < batch;  // idle lanes and frames past the batch: masked from the start
-        slot = mine ? wv * g.fpw + f : 0;
-        if (!mine) frame = 0;
-    } else {
-        r = (int)threadIdx.x;
-        frame = (int64_t)blockIdx.x;
-        mine = r < z;
+struct QcFixedRule {
+    using Geom = QcFixedGeom;
+    using IO = int8_t;
+    using Elem = int8_t;
+    uint32_t* CW;
+    int8_t* P;
+    PL_DEV QcFixedRule(const QcFixedGeom& g, unsigned char* base)
+        : CW(reinterpret_cast<uint32_t*>(base)), P(reinterpret_cast<int8_t*>(base + g.off_p)) {}
+    static PL_DEV int8_t load(const QcFixedGeom& g, int8_t x) { return (int8_t)qf_clamp((int)x, g.llr_max); }
+    template <int DCAP>
+    PL_DEV void update(const QcFixedGeom& g, const int32_t* __restrict__ pr, int d, int r, int c, bool first) const {
+        qf_check_update<DCAP>(g, pr, d, r, P, CW + (size_t)c * g.mw, first);
     }
-    unsigned char* const base = GLOBAL ? work + (size_t)frame * (size_t)g.state_bytes
-                                       : qf_smem + (size_t)slot * (size_t)g.state_bytes;
-    uint32_t* const CW = reinterpret_cast<uint32_t*>(base);
-    int8_t* const P = reinterpret_cast<int8_t*>(base + g.off_p);
-    uint32_t* const vote = reinterpret_cast<uint32_t*>(qf_smem + (GLOBAL ? 0 : g.state_bytes));  // block mapping: [2][16]
-    const int8_t* const lf = llr + frame * ld;
-    // the lanes that move a frame's P in and out: its Z lanes, or the whole workgroup
-    const bool io = SUBWAVE ? mine : true;
-    const int v0 = SUBWAVE ? r : (int)threadIdx.x, vstep = SUBWAVE ? z : (int)blockDim.x;
+};
 
-    if (io)
-        for (int v = v0; v < g.n; v += vstep) P[v] = (int8_t)qf_clamp((int)lf[v], g.llr_max);
-    lms_sync<SUBWAVE>();
+hipError_t qc_prepare(const QcFixedGeom& g) { return qc_frame_prepare<QcFixedRule>(g); }
 
-    bool live = mine;  // SUBWAVE: cleared when the lane's frame has stopped
-    int done = g.max_iter;
-    for (int it = 0; it < g.max_iter; ++it) {
-        const int32_t* t = tab;
-        for (int l = 0; l < g.mb; ++l) {
-            const int i = t[0], d = t[1];
-            if (d > 0) {  // the same in every lane
-                if (live) {
-                    const int c = i * z + r;
-                    qf_check_update<DCAP>(g, t + 2, d, r, P, CW + (size_t)c * g.mw, it == 0);
-                }
-                lms_sync<SUBWAVE>();
-            }
-            t += 2 + 2 * d;
-        }
-        if (g.early_stop) {
-            bool bad = false;
-            if (live) {
-                t = tab;
-                for (int l = 0; l < g.mb; ++l) {
-                    const int d = t[1];
-                    uint32_t par = 0;
-                    for (int j = 0; j < d; ++j) par ^= P[qf_var(t[2 + 2 * j], t[3 + 2 * j], r, z)] <= 0 ? 1u : 0u;
-                    bad |= par != 0u;
-                    t += 2 + 2 * d;
-                }
-            }
-            if (SUBWAVE) {
-                const unsigned long long badm = __ballot(bad);
-                lms_sync<true>();  // the next iteration's stores to P stay behind these loads
-                if (live) {
-                    const unsigned long long fm = (z == 64 ? ~0ull : ((1ull << z) - 1ull)) << (f * z);
-                    if ((badm & fm) == 0ull) { done = it + 1; live = false; }
-                }
-                if (__ballot(live) == 0ull) break;
-            } else {
-                if (!lms_wg_any(bad, vote, it & 1)) { done = it + 1; break; }
-            }
-        }
-    }
-
-    if (io) {
-        uint8_t* const bf = bits + frame * (int64_t)g.n;
-        for (int v = v0; v < g.n; v += vstep) {
-            const int8_t x = P[v];
-            bf[v] = x <= 0 ? 1 : 0;
-            if (post) post[frame * ld_post + v] = x;
-        }
-    }
-    if (iters && mine && r == 0) iters[frame] = done;
-}
-
-template <int DCAP>
-static void* qf_pick_at(const QcFixedGeom& g) {
-    if (g.subwave)
-        return g.use_global ? (void*)ldpc_qc_fixed_kernel<DCAP, true, true>
-                            : (void*)ldpc_qc_fixed_kernel<DCAP, true, false>;
-    return g.use_global ? (void*)ldpc_qc_fixed_kernel<DCAP, false, true>
-                        : (void*)ldpc_qc_fixed_kernel<DCAP, false, false>;
-}
-static void* qf_pick(const QcFixedGeom& g) {
-    switch (g.dcap) {
-        case 8: return qf_pick_at<8>(g);
-        case 16: return qf_pick_at<16>(g);
-        case 32: return qf_pick_at<32>(g);
-        default: return qf_pick_at<0>(g);
-    }
-}
-
-hipError_t qc_fixed_prepare(const QcFixedGeom& g) {
-    return hipFuncSetAttribute(qf_pick(g), hipFuncAttributeMaxDynamicSharedMemorySize, g.lds_bytes);
-}
-
-hipError_t qc_fixed_launch(const QcFixedGeom& g, const int32_t* tab, const int8_t* llr, int64_t ld, uint8_t* bits,
-                           int32_t* iters, int8_t* post, int64_t ld_post, int64_t batch, unsigned char* work,
-                           hipStream_t s) {
-    QcFixedGeom gg = g;
-    const int64_t fpg = (int64_t)g.fpw * g.fpb;  // frames per workgroup
-    void* args[] = {&gg, (void*)&tab, (void*)&llr, (void*)&ld, (void*)&bits, (void*)&iters, (void*)&post,
-                    (void*)&ld_post, (void*)&batch, (void*)&work};
-    return hipLaunchKernel(qf_pick(g), dim3((unsigned)((batch + fpg - 1) / fpg)), dim3(g.threads), args, g.lds_bytes, s);
+hipError_t qc_launch(const QcFixedGeom& g, const int32_t* tab, const int8_t* llr, int64_t ld, uint8_t* bits,
+                     int32_t* iters, int8_t* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s) {
+    return qc_frame_launch<QcFixedRule>(g, tab, llr, ld, bits, iters, post, ld_post, batch, work, s);
 }
 
 // ---- the quantiser: L = clamp(rint((double)llr * scale), -llr_max, llr_max), NaN -> 0 ----

@@ -1,5 +1,5 @@
 """QCLayeredMSDecoder(dtype=np.float32) -- the single-precision instances of
-ldpc_qc_kernel, PL_LDPC_QC_F32 -- against the NumPy float32 restatement of the
+qc_frame_kernel, PL_LDPC_QC_F32 -- against the NumPy float32 restatement of the
 layered definition (tests/layered_ref32.py) on the expanded H with the block
 rows as layers.  Bar everywhere: hard decisions and iteration counts
 array_equal, posteriors array_equal with equal_nan and dtype float32.
