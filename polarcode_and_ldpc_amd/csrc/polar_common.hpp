@@ -15,6 +15,10 @@ namespace pl {
 // sign of a zero result may differ from NumPy's, which never changes a value or
 // decision downstream (x + -0 = x + 0 for x != 0, and -0 >= 0).  Exact.
 // 7 VALU: cmp, 2 selects, xor + bfi for the sign, unordered cmp + select.
+// NANS = false: for operands that are never NaN (the tree kernel's list
+// instances, whose frames with a NaN LLR are decoded again by polar_nan.hip):
+// the same value without the last two.
+template <bool NANS = true>
 PL_DEV double f_ms(double a, double b) {
     const bool lt = fabs(b) < fabs(a);
     const uint64_t ua = (uint64_t)__double_as_longlong(a), ub = (uint64_t)__double_as_longlong(b);
@@ -22,7 +26,7 @@ PL_DEV double f_ms(double a, double b) {
     const uint32_t hs = lt ? (uint32_t)(ub >> 32) : (uint32_t)(ua >> 32);
     const uint32_t sg = (uint32_t)(ua >> 32) ^ (uint32_t)(ub >> 32);
     uint32_t hi = (hs & 0x7FFFFFFFu) | (sg & 0x80000000u);
-    hi = __builtin_isunordered(a, b) ? 0x7FF80000u : hi;
+    if constexpr (NANS) hi = __builtin_isunordered(a, b) ? 0x7FF80000u : hi;
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 // g: btm + top if bit == 0 else btm - top (one rounding, as the reference)

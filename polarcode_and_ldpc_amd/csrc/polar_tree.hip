@@ -28,7 +28,11 @@
 //       depth n        a register (the leaf LLR);
 //   * partial sums (beta) of depths n-5..n live in two registers per lane, the
 //     multi-word depths 1..n-6 in the workspace behind 5-bit slot pointers, as
-//     the LLR pools.  A list clone copies 24 bytes (rows + beta registers);
+//     the LLR pools (3-bit at list capacities <= 8 and n <= 10, TG::NARROW).  A
+//     list clone copies 24 bytes (rows + beta registers; 16 with narrow rows);
+//   * the leaf loop decodes leaves as (even, odd) pairs: an odd leaf's descent
+//     is one g over the depth n-1 pair and only its walk has steps, the frozen
+//     mask is held a 32-leaf word at a time (TG::PAIR, TG::FZW);
 //   * pruning: strict ranks from fp32 roundings of the metrics (ties and fp32
 //     collisions detected and redone exactly), read through DPP lane exchanges
 //     at LCAP 8 and from LDS with 16-byte broadcasts otherwise; survivors are
@@ -45,6 +49,7 @@
 #include "polar_common.hpp"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace pl {
 
@@ -105,15 +110,24 @@ template <int CTRL>
 PL_DEV int dpp_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, false); }
 constexpr int DPP_X1 = 0xB1, DPP_X2 = 0x4E, DPP_X3 = 0x1B, DPP_MIRROR8 = 0x141;
 // fn(x of lane slot ^ k) for k = 1..7 of the lane's 8-lane group
-template <class Fn>
+// FREE (TG::DPP_FREE): the exchange without a defined value for lanes the
+// control does not write.  Quad permutes and the half-row mirror write every
+// enabled lane and the wave runs with all lanes enabled, so the result is the
+// same; the zero that dpp_i passes as the old value costs a v_mov per exchange.
+template <int CTRL, bool FREE>
+PL_DEV int dpp_x(int x) {
+    if constexpr (FREE) return __builtin_amdgcn_mov_dpp(x, CTRL, 0xF, 0xF, true);
+    else return dpp_i<CTRL>(x);
+}
+template <bool FREE = false, class Fn>
 PL_DEV void group8_each(int x, Fn fn) {
-    const int m = dpp_i<DPP_MIRROR8>(x);
-    fn(dpp_i<DPP_X1>(x));
-    fn(dpp_i<DPP_X2>(x));
-    fn(dpp_i<DPP_X3>(x));
-    fn(dpp_i<DPP_X3>(m));
-    fn(dpp_i<DPP_X2>(m));
-    fn(dpp_i<DPP_X1>(m));
+    const int m = dpp_x<DPP_MIRROR8, FREE>(x);
+    fn(dpp_x<DPP_X1, FREE>(x));
+    fn(dpp_x<DPP_X2, FREE>(x));
+    fn(dpp_x<DPP_X3, FREE>(x));
+    fn(dpp_x<DPP_X3, FREE>(m));
+    fn(dpp_x<DPP_X2, FREE>(m));
+    fn(dpp_x<DPP_X1, FREE>(m));
     fn(m);
 }
 
@@ -221,8 +235,6 @@ PL_DEV bool ordered_prune(double m0, double m1, int slot, int lane) {
     ok = ok && (slot == 0 || Ap > A) && (slot + 1 < LCAP || A > mb);
     return __ballot(!ok) == 0;
 }
-
-constexpr int RB = 5;  // bits per slot field of a pointer row (list capacity <= 32)
 
 template <int NL, int LCAP_, int F_, int DL_, int DS_ = 0>
 struct TG {
@@ -340,6 +352,67 @@ struct TG {
     static constexpr bool FT_PF_IN = LCAP >= 16 || (LCAP == 8 && (PL_FT_PF_IN >= 0 ? PL_FT_PF_IN != 0 : WIDE));
     static_assert(!STAGE || 2 * FPW * GS >= 1024 * FT_CH, "metric/row scratch holds a staging chunk");
     static_assert(WS < (1LL << 31), "a wave's workspace slice is addressed with 32-bit offsets");
+    // ---- the leaf loop's control path (list instances; SC keeps the generic loop
+    // and its r0k skipping).  Seven of eight leaves touch no workspace pool, so
+    // what the loop spends around them is scalar control and row arithmetic:
+    //   PAIR: leaves are decoded as (even, odd) pairs with one copy of the
+    //        decision.  An odd leaf has dstart = n: its descent is descend_g<n-1>
+    //        called directly (no ws_sync test, no descend_from chain, an empty
+    //        set_range) and its walk has steps >= 1 (first step on bit 0 of bb,
+    //        no variable shifts).  An even leaf has 0 walk steps (beta_set<n>(n, bit))
+    //        and tests its parent depth from n-2 upwards (half of them stop at
+    //        the first compare);
+    //   FZW: the frozen mask word of 32 leaves held in an SGPR, the next one
+    //        fetched a block ahead; frozen / rate0_k read its bits (no scalar
+    //        load and wait at each leaf's decision);
+    //   NARROW: 3-bit slot fields in 32-bit pointer rows where the list
+    //        capacity and the depth allow (depths <= 9 fill 30 bits): the prune
+    //        exchange publishes (lrow, brow, bb, bw5) as one 16-byte LDS entry
+    //        instead of 16 + 8 bytes, and two VGPRs are freed.
+#ifndef PL_LEAF_PAIR
+#define PL_LEAF_PAIR -1  // -1: the per-instance rule
+#endif
+#ifndef PL_FZ_WORD
+#define PL_FZ_WORD -1
+#endif
+#ifndef PL_NARROW_ROWS
+#define PL_NARROW_ROWS -1
+#endif
+#ifndef PL_DPP_FREE
+#define PL_DPP_FREE -1
+#endif
+#ifndef PL_SURV_FLAT
+#define PL_SURV_FLAT -1
+#endif
+#ifndef PL_F_NAN
+#define PL_F_NAN -1
+#endif
+#ifndef PL_WALK_UNROLL
+#define PL_WALK_UNROLL -1
+#endif
+    static constexpr bool PAIR = LCAP > 1 && (PL_LEAF_PAIR >= 0 ? PL_LEAF_PAIR != 0 : true);
+    static constexpr bool FZW = LCAP > 1 && (PL_FZ_WORD >= 0 ? PL_FZ_WORD != 0 : true);
+    static constexpr bool NARROW = LCAP > 1 && LCAP <= 8 && n <= 10 && (PL_NARROW_ROWS >= 0 ? PL_NARROW_ROWS != 0 : true);
+    //   DPP_FREE: the rank exchanges at LCAP = 8 without a zero for unwritten
+    //        lanes (dpp_x): 16 v_mov fewer per pruning;
+    //   WALK_UNR (with PAIR): the walk's register steps (depths n-1..n-5) each
+    //        with compile-time widths and shifts (walk_reg) instead of a loop
+    //        over runtime ones: a step of 2^k bits spreads only those.
+    //   F_NAN = false: f without its NaN select (f_ms<false>).  A list instance
+    //        flags every frame in which an LLR can be NaN (a NaN input, or two
+    //        inputs of magnitude >= 2^1000: the staging pass above the leaf
+    //        loop) and polar_nan.hip decodes it again, so in the frames whose
+    //        bits this kernel delivers no f ever sees a NaN.  SC has no such
+    //        second pass and keeps the select.
+    static constexpr bool F_NAN = LCAP == 1 || (PL_F_NAN >= 0 ? PL_F_NAN != 0 : false);
+    //   SURV_FLAT: the tie check's two claim read-backs without short circuit.
+    static constexpr bool SURV_FLAT = LCAP > 1 && (PL_SURV_FLAT >= 0 ? PL_SURV_FLAT != 0 : LCAP == 8);
+    static constexpr bool DPP_FREE = LCAP == 8 && (PL_DPP_FREE >= 0 ? PL_DPP_FREE != 0 : true);
+    static constexpr bool WALK_UNR = PAIR && (PL_WALK_UNROLL >= 0 ? PL_WALK_UNROLL != 0 : true);
+    static constexpr int RB = NARROW ? 3 : 5;  // bits per slot field of a pointer row
+    using Row = std::conditional_t<NARROW, uint32_t, uint64_t>;
+    static constexpr int ROW_FIELDS = NARROW ? 10 : 12;
+    static_assert(RB * ROW_FIELDS <= (int)sizeof(Row) * 8 && n <= ROW_FIELDS && LCAP <= (1 << RB), "pointer row fields");
 };
 
 // ---- scalar-base addressing (TG::BUF) --------------------------------------
@@ -409,13 +482,18 @@ struct Span {
     }
 };
 
-PL_DEV int field(uint64_t row, int d) { return (int)((row >> (RB * d)) & 31u); }
-PL_DEV uint64_t set_field(uint64_t row, int d, int v) {
-    return (row & ~(31ull << (RB * d))) | ((uint64_t)v << (RB * d));
+// Pointer rows: field d (RB bits, TG::RB) is the slot whose pool of depth d the path reads
+template <int RB, class Row>
+PL_DEV int field(Row row, int d) { return (int)((row >> (RB * d)) & (Row)((1u << RB) - 1u)); }
+template <int RB, class Row>
+PL_DEV Row set_field(Row row, int d, int v) {
+    return (row & ~((Row)((1u << RB) - 1u) << (RB * d))) | ((Row)v << (RB * d));
 }
-PL_DEV uint64_t set_range(uint64_t row, uint64_t own, int lo, int hi) {  // fields [lo, hi) := own
-    const uint64_t h = (RB * hi >= 64) ? ~0ull : ((1ull << (RB * hi)) - 1ull);
-    const uint64_t m = h & ~((1ull << (RB * lo)) - 1ull);
+template <int RB, class Row>
+PL_DEV Row set_range(Row row, Row own, int lo, int hi) {  // fields [lo, hi) := own
+    constexpr int BITS = (int)sizeof(Row) * 8;
+    const Row h = (RB * hi >= BITS) ? (Row)~(Row)0 : (Row)(((Row)1 << (RB * hi)) - (Row)1);
+    const Row m = h & ~(Row)(((Row)1 << (RB * lo)) - (Row)1);
     return (row & ~m) | (own & m);
 }
 
@@ -433,6 +511,27 @@ PL_DEV void beta_set(int d, uint32_t v, uint32_t& bb, uint32_t& bw5) {
     if (k == 5) { bw5 = v; return; }
     const uint32_t m = ((1u << (1 << k)) - 1u) << ((1 << k) - 1);
     bb = (bb & ~m) | ((v << ((1 << k) - 1)) & m);
+}
+
+// The walk of an odd leaf from its step K (1..5) on, `steps` in all, while the
+// left siblings' partial sums are in registers (depths n-K): cur holds the
+// 2^K bits of depth n-K's right child.  True when the walk ended there (the
+// result a left child kept in registers); false with cur = the word of depth
+// n-5's right child when steps > 5.
+template <int n, int K>
+PL_DEV bool walk_reg(int steps, uint32_t& cur, uint32_t& bb, uint32_t& bw5) {
+    if (steps == K) {
+        beta_set<n>(n - K, cur, bb, bw5);
+        return true;
+    }
+    if constexpr (K == 5) {
+        return false;
+    } else {
+        constexpr uint32_t msk = (1u << (1 << K)) - 1u;
+        const uint32_t left = beta_get<n>(n - K, bb, bw5);
+        cur = spread16((left ^ cur) & msk) | (spread16(cur & msk) << 1);
+        return walk_reg<n, K + 1>(steps, cur, bb, bw5);
+    }
 }
 
 // Global workspace written by other lanes of this wave: wait for this wave's
@@ -474,7 +573,7 @@ PL_DEV void fold(Fold<G>& st, double v, int idx, unsigned char* smem, const Span
                                                              st.pend[D], v);
                 }
             }
-            fold<G, D + 1>(st, f_ms(st.pend[D], v), idx >> 1, smem, ws, plane);
+            fold<G, D + 1>(st, f_ms<G::F_NAN>(st.pend[D], v), idx >> 1, smem, ws, plane);
         } else {
             st.pend[D] = v;
         }
@@ -632,7 +731,7 @@ PL_DEV double fused_loop(unsigned char* smem, const Span<G::BUF>& ws, int lane, 
                         for (int k = 0; k < m; ++k) v[k] = g_op(v[2 * k], v[2 * k + 1], b >> k);
                     } else {
 #pragma unroll
-                        for (int k = 0; k < m; ++k) v[k] = f_ms(v[2 * k], v[2 * k + 1]);
+                        for (int k = 0; k < m; ++k) v[k] = f_ms<G::F_NAN>(v[2 * k], v[2 * k + 1]);
                     }
                 }
                 fold<G, F>(st, v[0], t, smem, ws, plane);
@@ -671,7 +770,7 @@ PL_DEV double fused_loop(unsigned char* smem, const Span<G::BUF>& ws, int lane, 
                 for (int k = 0; k < m; ++k) v[k] = g_op(v[2 * k], v[2 * k + 1], b >> k);
             } else {
 #pragma unroll
-                for (int k = 0; k < m; ++k) v[k] = f_ms(v[2 * k], v[2 * k + 1]);
+                for (int k = 0; k < m; ++k) v[k] = f_ms<G::F_NAN>(v[2 * k], v[2 * k + 1]);
             }
         }
         fold<G, F>(st, v[0], t, smem, ws, plane);
@@ -681,7 +780,7 @@ PL_DEV double fused_loop(unsigned char* smem, const Span<G::BUF>& ws, int lane, 
 
 template <class G>
 PL_DEV double descend_fused(unsigned char* smem, const Span<G::BUF>& ws, int lane, int fw, int plane, int i,
-                            const Chan<G>& ch, uint64_t brow, uint32_t bb, uint32_t bw5, uint32_t skip = 0) {
+                            const Chan<G>& ch, typename G::Row brow, uint32_t bb, uint32_t bw5, uint32_t skip = 0) {
     constexpr int n = G::n, F = G::F;
     bool right[F + 1];
     uint32_t bsl[F + 1];  // the lane's byte offset in the partial-sum pool of depth d
@@ -689,7 +788,7 @@ PL_DEV double descend_fused(unsigned char* smem, const Span<G::BUF>& ws, int lan
 #pragma unroll
     for (int d = 1; d <= F; ++d) {
         right[d] = (i >> (n - d)) & 1;
-        bsl[d] = (uint32_t)G::pl(field(brow, d), fw) * 4;
+        bsl[d] = (uint32_t)G::pl(field<G::RB>(brow, d), fw) * 4;
         bw[d] = (d > G::NB) ? beta_get<n>(d, bb, bw5) : 0u;
     }
     if constexpr (G::NS >= 3) {
@@ -707,19 +806,22 @@ PL_DEV double descend_fused(unsigned char* smem, const Span<G::BUF>& ws, int lan
 // Size 2^k (k <= 3) of the rate-0 node (all leaves frozen) whose first leaf is
 // decode-order leaf i, 0 if none: i a multiple of 2^k, leaves i .. i+2^k-1
 // frozen (one mask word holds them).
-PL_DEV int rate0_k(const uint32_t* __restrict__ frozen_dec, int i) {
-    const uint32_t w = frozen_dec[i >> 5] >> (i & 31);
+// (w: the frozen mask word shifted so that leaf i is bit 0)
+PL_DEV int rate0_k_bits(uint32_t w, int i) {
     return ((i & 7) == 0 && (w & 0xFFu) == 0xFFu)  ? 3
            : ((i & 3) == 0 && (w & 0xFu) == 0xFu) ? 2
            : ((i & 1) == 0 && (w & 3u) == 3u)     ? 1
                                                   : 0;
+}
+PL_DEV int rate0_k(const uint32_t* __restrict__ frozen_dec, int i) {
+    return rate0_k_bits(frozen_dec[i >> 5] >> (i & 31), i);
 }
 
 // Leaf LLRs of a rate-0 node (every leaf frozen, so every partial sum inside
 // it is 0 and the g of a right child is btm + top): the leaves of A are the
 // leaves of its f-child, then those of its g-child -- the very f / g the leaf
 // by leaf schedule evaluates on the same operands.
-template <int S>
+template <int S, bool NANS = true>
 PL_DEV void rate0_leaves(const double* A, double* out) {
     if constexpr (S == 1) {
         out[0] = A[0];
@@ -727,11 +829,11 @@ PL_DEV void rate0_leaves(const double* A, double* out) {
         double L[S / 2], R[S / 2];
 #pragma unroll
         for (int t = 0; t < S / 2; ++t) {
-            L[t] = f_ms(A[2 * t], A[2 * t + 1]);
+            L[t] = f_ms<NANS>(A[2 * t], A[2 * t + 1]);
             R[t] = g_op(A[2 * t], A[2 * t + 1], 0u);
         }
-        rate0_leaves<S / 2>(L, out);
-        rate0_leaves<S / 2>(R, out + S / 2);
+        rate0_leaves<S / 2, NANS>(L, out);
+        rate0_leaves<S / 2, NANS>(R, out + S / 2);
     }
 }
 
@@ -754,7 +856,7 @@ PL_DEV void rate0_rest(const unsigned char* smem, const Span<G::BUF>& ws, int pl
             a[2 * j] = pr.x;
             a[2 * j + 1] = pr.y;
         }
-        rate0_leaves<S>(a, ll);
+        rate0_leaves<S, G::F_NAN>(a, ll);
         // increments of two leaves evaluated together (independent chains),
         // always computed: where path_metrics_fast skips t it is below a quarter
         // ulp of every addend and the sums are the same
@@ -774,6 +876,29 @@ PL_DEV void rate0_rest(const unsigned char* smem, const Span<G::BUF>& ws, int pl
             for (int u = 0; u < IL; ++u)
                 if (j0 + u < S && active) pm = pm + inc[u];
         }
+    }
+}
+
+// The same dispatch from the deepest parent depth upwards (TG::PAIR, even
+// leaves: p = n-2 for half of them, n-3 for a quarter, ...), with what depends
+// on the depth done inside it at compile-time shifts: the parent's slot (field
+// p of lrow), the partial sums' slot (field p+1 of brow) and the row update
+// (fields p+1..n-1 of lrow := rown, the lane's own slot or 0 for a shadow).
+template <class G, int P>
+PL_DEV double descend_from_deep(int p, unsigned char* smem, const Span<G::BUF>& ws, int plane, int fw,
+                                typename G::Row& lrow, typename G::Row brow, typename G::Row rown, uint32_t bb,
+                                uint32_t bw5, uint32_t skip = 0) {
+    if constexpr (P < G::F) {
+        return 0.0;
+    } else {
+        if (p == P) {
+            const int ps = G::pl(field<G::RB>(lrow, P), fw);
+            const int bs = G::pl(field<G::RB>(brow, P + 1 <= G::NB ? P + 1 : 0), fw);
+            const double lam = descend_g<G, P>(smem, ws, plane, ps, bs, bb, bw5, skip);
+            lrow = set_range<G::RB>(lrow, rown, P + 1, G::n);
+            return lam;
+        }
+        return descend_from_deep<G, P - 1>(p, smem, ws, plane, fw, lrow, brow, rown, bb, bw5, skip);
     }
 }
 
@@ -820,11 +945,14 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
     // slot 0 stores to the same addresses -- no memory traffic of its own.
     // the wave's own slice, and nothing past it
     const Span<G::BUF> ws(workspace + (size_t)blockIdx.x * G::WS, (uint32_t)G::WS);
-    uint64_t own = 0;
+    using Row = typename G::Row;
+    constexpr int RB = G::RB;
+    Row own = 0;
 #pragma unroll
-    for (int d = 0; d < 12; ++d) own |= (uint64_t)slot << (RB * d);
+    for (int d = 0; d < G::ROW_FIELDS; ++d) own |= (Row)slot << (RB * d);
     double2* const met = reinterpret_cast<double2*>(smem + G::L_MET + fw * G::GS);    // [LCAP] of this frame
     uint64_t* const rowx = reinterpret_cast<uint64_t*>(smem + G::L_ROW + fw * G::GS);  // [LCAP][2]
+    uint4* const rowx4 = reinterpret_cast<uint4*>(rowx);  // TG::NARROW: [LCAP] (lrow, brow, bb, bw5)
     uint64_t* const brx = reinterpret_cast<uint64_t*>(smem + G::L_BR) + base;          // [LCAP]
     uint32_t* const surv = reinterpret_cast<uint32_t*>(smem + G::L_SURV) + base;       // [LCAP]
     // the lane's byte offset in the walk buffers ([2][CW][64] u32 at W_WALK) as path slot s
@@ -932,7 +1060,7 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                     }
                     if (d < G::NS) {
 #pragma unroll
-                        for (int k = 0; k < np; ++k) v[k] = f_ms(v[2 * k], v[2 * k + 1]);
+                        for (int k = 0; k < np; ++k) v[k] = f_ms<G::F_NAN>(v[2 * k], v[2 * k + 1]);
                     }
                 }
             }
@@ -956,15 +1084,26 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                              (unsigned long long)fm);
             }
         }
-        uint64_t lrow = G::SHADOW ? 0 : own, brow = lrow;  // shadows start on slot 0's rows
+        Row lrow = G::SHADOW ? 0 : own, brow = lrow;  // shadows start on slot 0's rows
         uint32_t bb = 0, bw5 = 0;
         double pm = (slot == 0) ? 0.0 : -INFINITY;
         int nact = 1;
         int root_par = 0;
         STAMP(7);
         int nextK = (SC && r0k) ? (int)(r0k[0] & 15u) : 0;  // SC: r0k of the next leaf (scalar load, a leaf ahead)
+        // TG::FZW: the frozen mask word of leaves 32 b .. 32 b + 31 and the next
+        // block's, fetched a block ahead (a rate-0 node never crosses a word)
+        uint32_t fzw = 0, fznext = G::FZW ? frozen_dec[0] : 0u;
 
         for (int i = 0; i < N; ++i) {
+            if constexpr (G::FZW) {
+                if ((i & 31) == 0) {
+                    fzw = fznext;
+                    fznext = frozen_dec[(i >> 5) + 1 < G::CW ? (i >> 5) + 1 : G::CW - 1];
+                }
+            }
+            // TG::PAIR: leaf i is the odd leaf of its pair (wave-uniform)
+            const bool odd = G::PAIR && (i & 1);
             // ================================================ LLRs down to leaf i
             const int dstart = (i == 0) ? 1 : n - __builtin_ctz(i);
             const int pslot = (!G::SHADOW || slot < nact) ? slot : 0;  // shadows use slot 0's planes
@@ -1005,29 +1144,43 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                     }
                 }
             }
-            if (!skip_descend) {
+            if (odd) {
+                // dstart = n: the parents are the depth n-1 pair in LDS (DL <= n-1)
+                // that the even leaf's descent stored, no pointer field changes
+                STAMP(7);
+                lam = descend_g<G, n - 1>(smem, ws, plane, G::pl(field<RB>(lrow, n - 1), fw), 0, bb, bw5, dskip);
+                STAMP(2);
+            } else if (!skip_descend) {
                 if (dstart <= DL) ws_sync();  // workspace written by other lanes
                 STAMP(7);
                 if (dstart <= F) {
                     lam = descend_fused<G>(smem, ws, lane, fw, plane, i, ch, brow, bb, bw5, dskip);
-                    lrow = set_range(lrow, (!G::SHADOW || slot < nact) ? own : 0ull, F, n);
+                    lrow = set_range<RB>(lrow, (!G::SHADOW || slot < nact) ? own : (Row)0, F, n);
                     STAMP(0);
                 } else {
                     const int p = dstart - 1;
-                    const int ps = G::pl(field(lrow, p), fw);
-                    const int bs = G::pl(field(brow, dstart <= G::NB ? dstart : 0), fw);
-                    if constexpr (DS == 1) {
-                        if (p >= F && p < DL)
-                            atomicOr(dsm + ((1 << p) - (1 << F) + (i >> (n - p))) * 2 + (ps >> 5), 1u << (ps & 31));
+                    const Row rown = (!G::SHADOW || slot < nact) ? own : (Row)0;
+                    if constexpr (G::PAIR && DS != 1) {
+                        // the parent depth decided once: slots and the row update
+                        // with compile-time fields inside the dispatch
+                        lam = descend_from_deep<G, n - 2>(p, smem, ws, plane, fw, lrow, brow, rown, bb, bw5, dskip);
+                    } else {
+                        const int ps = G::pl(field<RB>(lrow, p), fw);
+                        const int bs = G::pl(field<RB>(brow, dstart <= G::NB ? dstart : 0), fw);
+                        if constexpr (DS == 1) {
+                            if (p >= F && p < DL)
+                                atomicOr(dsm + ((1 << p) - (1 << F) + (i >> (n - p))) * 2 + (ps >> 5), 1u << (ps & 31));
+                        }
+                        lam = descend_from<G, F>(p, smem, ws, plane, ps, bs, bb, bw5, dskip);
+                        lrow = set_range<RB>(lrow, rown, dstart, n);
                     }
-                    lam = descend_from<G, F>(p, smem, ws, plane, ps, bs, bb, bw5, dskip);
-                    lrow = set_range(lrow, (!G::SHADOW || slot < nact) ? own : 0ull, dstart, n);
                     if (p < DL) { STAMP(1); } else { STAMP(2); }
                 }
             }
 
             // ================================================ decision at leaf i
-            const bool frozen = (frozen_dec[i >> 5] >> (i & 31)) & 1u;
+            const uint32_t fzbits = G::FZW ? fzw >> (i & 31) : frozen_dec[i >> 5] >> (i & 31);  // leaf i at bit 0
+            const bool frozen = fzbits & 1u;
             int bit;
             if constexpr (SC) {
                 bit = frozen ? 0 : (lam >= 0.0 ? 0 : 1);
@@ -1067,9 +1220,13 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                 constexpr bool BITONIC = F32 && LCAP == 32;
                 if constexpr (F32 && !DPP && !BITONIC) reinterpret_cast<float2*>(met)[slot] = make_float2((float)m0, (float)m1);
                 else met[slot] = make_double2(m0, m1);
-                rowx[2 * slot] = lrow;
-                rowx[2 * slot + 1] = brow;
-                brx[slot] = (uint64_t)bb | ((uint64_t)bw5 << 32);
+                if constexpr (G::NARROW) {
+                    rowx4[slot] = make_uint4((uint32_t)lrow, (uint32_t)brow, bb, bw5);
+                } else {
+                    rowx[2 * slot] = lrow;
+                    rowx[2 * slot + 1] = brow;
+                    brx[slot] = (uint64_t)bb | ((uint64_t)bw5 << 32);
+                }
                 if constexpr (!DPP && !BITONIC) lds_sync();
                 // rank of (slot, b) in the stable descending order of
                 // [(m0, q) for active q] + [(m1, q) for active q]
@@ -1154,8 +1311,8 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                             r0 += c > f0;
                             r1 += c > f1;
                         };
-                        group8_each(__float_as_int(f0), cmp);
-                        group8_each(__float_as_int(f1), cmp);
+                        group8_each<G::DPP_FREE>(__float_as_int(f0), cmp);
+                        group8_each<G::DPP_FREE>(__float_as_int(f1), cmp);
                     } else if constexpr (F32) {
                         const float f0 = (float)m0, f1 = (float)m1;
                         const float2* const met32 = reinterpret_cast<const float2*>(met);
@@ -1191,8 +1348,17 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                     // fp64 metrics over the fp32 copies (all read before the sync)
                     if constexpr (F32 && !DPP) met[slot] = make_double2(m0, m1);
                     // a lost claim = a tie; the survivor entry is read in the same trip
-                    const bool lost =
-                        slot < nact && ((r0 < nsurv && surv[r0] != id0) || (r1 < nsurv && surv[r1] != id1));
+                    bool lost;
+                    if constexpr (G::SURV_FLAT) {
+                        // both claims read back unconditionally (index clamped into
+                        // the frame's table, the value ignored past the survivors):
+                        // one LDS trip with the survivor entry instead of two
+                        // dependent ones under nested lane masks
+                        const uint32_t c0 = surv[r0 < LCAP ? r0 : LCAP - 1], c1 = surv[r1 < LCAP ? r1 : LCAP - 1];
+                        lost = (slot < nact) & (((r0 < nsurv) & (c0 != id0)) | ((r1 < nsurv) & (c1 != id1)));
+                    } else {
+                        lost = slot < nact && ((r0 < nsurv && surv[r0] != id0) || (r1 < nsurv && surv[r1] != id1));
+                    }
                     e = surv[tgt];
                     if (__ballot(lost)) {
                         lds_sync();  // the fp64 metrics of every lane; surv reads done
@@ -1219,11 +1385,19 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                     bit = (int)(e & 1u);
                     const double2 pmv = met[par];
                     pm = slot < nsurv ? (bit ? pmv.y : pmv.x) : -INFINITY;
-                    lrow = rowx[2 * par];
-                    brow = rowx[2 * par + 1];
-                    const uint64_t br = brx[par];
-                    bb = (uint32_t)br;
-                    bw5 = (uint32_t)(br >> 32);
+                    if constexpr (G::NARROW) {
+                        const uint4 rx = rowx4[par];
+                        lrow = (Row)rx.x;
+                        brow = (Row)rx.y;
+                        bb = rx.z;
+                        bw5 = rx.w;
+                    } else {
+                        lrow = (Row)rowx[2 * par];
+                        brow = (Row)rowx[2 * par + 1];
+                        const uint64_t br = brx[par];
+                        bb = (uint32_t)br;
+                        bw5 = (uint32_t)(br >> 32);
+                    }
                 } else {
                     pm = -INFINITY;  // LCAP = 16: inactive slots keep their own state
                     bit = 0;
@@ -1248,7 +1422,7 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                 nextK = (r0k && i + 1 < N) ? (int)((r0k[(i + 1) >> 3] >> (4 * ((i + 1) & 7))) & 15u) : 0;
             } else {
                 if (frozen) {
-                    const int k = rate0_k(frozen_dec, i);
+                    const int k = G::FZW ? rate0_k_bits(fzbits, i) : rate0_k(frozen_dec, i);
                     if (k > 0) {
                         const int pslot = (!G::SHADOW || slot < nact) ? slot : 0;
                         const int plane = G::pl(pslot, fw);
@@ -1263,7 +1437,10 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
             }
 
             // ================================================ partial-sum walk
-            {
+            if (G::PAIR && !(i & 1)) {
+                // an even leaf is a left child: 0 steps, its bit is depth n's partial sum
+                beta_set<n>(n, (uint32_t)bit, bb, bw5);
+            } else {
                 const int to = __builtin_ctz(~(unsigned)i);
                 const int steps = to < n ? to : n;
                 // SC, skipped node of 2^skipK leaves: the walk starts at the node's
@@ -1271,13 +1448,25 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                 int dd = n - skipK;
                 uint32_t cur = (uint32_t)bit;
                 int k = skipK;
+                bool done = false;
+                if constexpr (G::PAIR) {
+                    // an odd leaf: steps >= 1, the first against the even leaf's bit (bit 0 of bb)
+                    cur = ((bb ^ cur) & 1u) | (cur << 1);
+                    dd = n - 1;
+                    k = 1;
+                    if constexpr (G::WALK_UNR) {
+                        done = walk_reg<n, 1>(steps, cur, bb, bw5);
+                        dd = n - 5;
+                        k = 5;
+                    }
+                }
                 if (SC && skipK > 5 && k == steps) {
                     // the node is a left child at a multi-word depth: store its
                     // zero words as that depth's partial sums (read by the right
                     // sibling's g), nothing to combine
                     for (int w = 0; w < (1 << (skipK - 5)); ++w)
                         ws.st_word(G::pl(slot, fw) * 4, (uint32_t)G::bl_off(dd) + w * 256, 0u);
-                    brow = set_field(brow, dd, slot);
+                    brow = set_field<G::RB>(brow, dd, slot);
                     k = steps + 1;  // done (no register store either)
                 }
                 for (; k < steps && k < 5; ++k) {
@@ -1286,8 +1475,8 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                     cur = spread16((left ^ cur) & msk) | (spread16(cur & msk) << 1);
                     --dd;
                 }
-                if (k > steps) {
-                    // SC skipped node stored above
+                if (done || k > steps) {
+                    // SC skipped node stored above; TG::WALK_UNR: stored by walk_reg
                 } else if (k == steps) {
                     beta_set<n>(dd, cur, bb, bw5);  // dd >= n-5: a left child, kept in registers
                 } else {
@@ -1304,7 +1493,7 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                     }
                     for (; k < steps; ++k) {
                         const int cwc = 1 << (k - 5);
-                        const int ls = G::pl(field(brow, dd <= G::NB ? dd : 0), fw);
+                        const int ls = G::pl(field<G::RB>(brow, dd <= G::NB ? dd : 0), fw);
                         const bool last = (k + 1 == steps);
                         const uint32_t lsrcu = (uint32_t)G::bl_off(dd <= G::NB ? dd : 1);
                         // word j of the step's input gives output words 2j, 2j+1
@@ -1341,7 +1530,7 @@ polar_tree_kernel(const double* __restrict__ llr, int64_t ld, uint8_t* __restric
                         --dd;
                     }
                     if (dd == 0) root_par = parity;
-                    else brow = set_field(brow, dd, wslot);
+                    else brow = set_field<G::RB>(brow, dd, wslot);
                 }
             }
             lds_sync();
