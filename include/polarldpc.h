@@ -769,6 +769,68 @@ int pl_polar_rate_match(const pl_polar_rm* rm, const uint8_t* cw_dev, int64_t ld
 int pl_polar_rate_recover(const pl_polar_rm* rm, const void* llr_dev, int64_t ld_llr, int64_t batch, double* out_dev,
                           int64_t ld_out, double known_llr, int32_t flags, void* stream);
 
+/* ---- Gray-mapped square QAM: modulator, complex AWGN, max-log soft demapper ----------
+ * What crosses the channel between a rate matcher's E transmitted bits and the E LLRs it
+ * takes back, when it is not one BPSK symbol per bit (pl_awgn_llr).  This comment is the
+ * definition; the kernels (qam.hip), channel.QAMModem and the harness cite it.  The
+ * mapping is built here from the binary-reflected Gray code; no standard's table is
+ * reproduced.
+ * Parameters and conditions; a violation is PL_EINVAL naming the first one violated, in
+ * this order:
+ *   1. m, bits per symbol, is 2, 4, 6 or 8 (QPSK, 16-, 64-, 256-QAM)
+ *   2. 1 <= E <= 2^30, transmitted bits per frame
+ * Derived: h = m / 2 bits per axis; S = ceil(E / m) symbols per frame; bits E .. S m - 1
+ * of the last symbol are zeros at the modulator and get no LLR.
+ * Bit to axis: bit i (0 .. m-1) of symbol s is e[s m + i] & 1.  Even i go to the I axis,
+ *   odd i to the Q axis; the bit's position on its axis is p = i / 2, p = 0 first.
+ * Axis mapping (Gray): from the axis bits b_0 .. b_(h-1): c_0 = b_0, c_p = c_(p-1) ^ b_p,
+ *   idx = sum c_p 2^(h-1-p), integer level a = (2^h - 1) - 2 idx.  All-zero bits give the
+ *   largest positive level (consistent with BPSK's 0 -> +1); neighbouring levels differ in
+ *   exactly one bit.
+ * Scale: D = 2 (4^h - 1) / 3, an exact integer (2, 10, 42, 170); scale = 1.0 / sqrt((double)D);
+ *   the axis value is x = (double)a * scale, one multiplication.  The constellation has unit
+ *   mean energy.
+ * Symbol layout: fp64, I and Q interleaved, [batch][ld] with ld >= 2 S: element 2 s is I
+ *   and element 2 s + 1 is Q of symbol s.
+ * Channel: y = x + sigma z per axis, sigma = sqrt(1 / (2 10^(snr_db / 10))) computed as
+ *   pl_awgn_llr computes it; snr_db is Es/N0 per QAM symbol.  The normals are the
+ *   Box-Muller pair of the stream contract (pl_awgn_llr's: two 53-bit uniforms of one
+ *   Philox4x32-10 call) at counter (s, f_lo, f_hi, 0x9A3A9A3A), f = frame_offset + b, key
+ *   as the AWGN source (seed_lo ^ 0x5bd1e995, seed_hi): z0 -> I, z1 -> Q of symbol s.  A
+ *   frame's values depend on (seed, frame_offset + b, s) only.
+ * Demapper (max-log), exact fp64, every step one IEEE operation, no contraction.  For an
+ *   axis value r and axis bit p: t = r - x_a, d_a = t * t for each of the 2^h levels; d0 =
+ *   min d_a over the levels whose bit p is 0, d1 over those whose bit p is 1; s2 = sigma *
+ *   sigma, w = 1.0 / (2.0 * s2) (on the host); llr = (d1 - d0) * w.  Positive decides 0.
+ *   PL_QAM_LLR_F32: the fp64 result rounded once to fp32, to nearest even.  A NaN r, or
+ *   an r so large that every d_a overflows, gives NaN (payload unspecified).
+ * pl_qam_check makes no device call; S_out and scale_out may be NULL.  There is no device
+ * object: the kernels take the parameters by value, and each entry point checks them
+ * again itself. */
+int pl_qam_check(int32_t m, int64_t E, int64_t* S_out, double* scale_out);
+/* x[b][2 s], x[b][2 s + 1] = the clean symbol s of e[b][0:E]: e_dev uint8 [batch][ld_e], ld_e >= E
+ * (bit 0 of each byte); x_dev double [batch][ld_x], ld_x >= 2 S, elements beyond 2 S are left
+ * alone.  Asynchronous on `stream`; batch == 0 launches nothing.  PL_EINVAL for what
+ * pl_qam_check refuses, batch < 0, a NULL pointer with batch > 0, a pointer that is not
+ * aligned to its element type and a short pitch; every check runs before the first device
+ * call. */
+int pl_qam_modulate(int32_t m, int64_t E, int64_t batch, const uint8_t* e_dev, int64_t ld_e, double* x_dev,
+                    int64_t ld_x, void* stream);
+/* y = x + sigma z as defined above, mapped and disturbed in one pass: y_dev double
+ * [batch][ld_y], ld_y >= 2 S.  e_dev == NULL: all-zero bits (ld_e is then not used).
+ * PL_EINVAL as pl_qam_modulate (y_dev NULL with batch > 0), and for a snr_db that is not
+ * finite. */
+int pl_qam_awgn(int32_t m, int64_t E, int64_t batch, const uint8_t* e_dev, int64_t ld_e, double snr_db, uint64_t seed,
+                int64_t frame_offset, double* y_dev, int64_t ld_y, void* stream);
+#define PL_QAM_LLR_F32 1 /* llr_dev is float (else double) */
+/* llr[b][t], t < E, of the received y_dev double [batch][ld_y], ld_y >= 2 S: llr_dev
+ * [batch][ld_llr], ld_llr >= E, elements beyond E are left alone; pitches in elements.
+ * PL_EINVAL as pl_qam_awgn, and for unknown flag bits.  The kernel cuts each row at the
+ * 16-byte boundaries of its output addresses and stores whole pieces 16 bytes wide,
+ * whatever the pointer and the pitch. */
+int pl_qam_demap(int32_t m, int64_t E, int64_t batch, const double* y_dev, int64_t ld_y, double snr_db, void* llr_dev,
+                 int64_t ld_llr, int32_t flags, void* stream);
+
 /* Error counting (benchmarks/ber_simulation.py:180-189):
  * counts_dev[0] += bit errors, [1] += frame errors, [2] += frames, over the
  * first `width` entries of each row.  counts_dev int64[3], device. */

@@ -34,11 +34,13 @@ EXPORTS = (
     "pl_ldpc_rate_recover", "pl_ldpc_qc_fixed_plan_create", "pl_ldpc_decode_i8", "pl_llr_quantize",
     "pl_debug_ldpc_qc_fixed_plan_probe", "pl_polar_rate_match_check", "pl_debug_polar_rate_match_probe",
     "pl_polar_rate_match_forced", "pl_polar_rate_match", "pl_polar_rate_recover",
+    "pl_qam_check", "pl_qam_modulate", "pl_qam_awgn", "pl_qam_demap",
 )
 PL_QUANT_LLR_F32 = 1  # pl_llr_quantize flag: llr_dev is float (else double)
 PL_RM_LLR_F32, PL_RM_OUT_F32, PL_RM_ACCUMULATE = 1, 2, 4  # pl_ldpc_rate_recover flags
 PL_PRM_PUNCTURE, PL_PRM_SHORTEN = 0, 1  # pl_polar_rm.mode
 PL_PRM_LLR_F32, PL_PRM_ACCUMULATE = 1, 4  # pl_polar_rate_recover flags
+PL_QAM_LLR_F32 = 1  # pl_qam_demap flag: llr_dev is float (else double)
 
 
 class PlanInfo(ctypes.Structure):
@@ -136,6 +138,10 @@ def _load(path=LIB_PATH):
     L.pl_polar_rate_match_forced.argtypes = [ctypes.POINTER(PolarRateMatch), P]
     L.pl_polar_rate_match.argtypes = [ctypes.POINTER(PolarRateMatch), P, I64, I64, P, I64, P]
     L.pl_polar_rate_recover.argtypes = [ctypes.POINTER(PolarRateMatch), P, I64, I64, P, I64, D, I32, P]
+    L.pl_qam_check.argtypes = [I32, I64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]
+    L.pl_qam_modulate.argtypes = [I32, I64, I64, P, I64, P, I64, P]
+    L.pl_qam_awgn.argtypes = [I32, I64, I64, P, I64, D, ctypes.c_uint64, I64, P, I64, P]
+    L.pl_qam_demap.argtypes = [I32, I64, I64, P, I64, D, P, I64, I32, P]
     L.pl_ldpc_decode_soft.argtypes = [P, P, I64, I64, P, P, P, I64, P]
     L.pl_ldpc_decode_f32.argtypes = [P, P, I64, I64, P, P, P, I64, P, I64, P]
     L.pl_decode.argtypes = [P, P, I64, I64, P, P, P]
@@ -546,6 +552,34 @@ def polar_rate_recover(rm: PolarRateMatch, llr: "torch.Tensor", out: "torch.Tens
     flags = (PL_PRM_LLR_F32 if llr.dtype == torch.float32 else 0) | (PL_PRM_ACCUMULATE if accumulate else 0)
     check(lib.pl_polar_rate_recover(ctypes.byref(rm), llr.data_ptr(), _ld(llr), llr.shape[0], out.data_ptr(), _ld(out),
                                     float(known_llr), flags, _stream(stream)), "pl_polar_rate_recover")
+
+
+def qam_check(m: int, E: int):
+    """pl_qam_check: (S, scale) of m bits per symbol and E transmitted bits (no device call).
+    AssertionError with the first violated condition."""
+    S, scale = ctypes.c_int64(), ctypes.c_double()
+    check(lib.pl_qam_check(int(m), int(E), ctypes.byref(S), ctypes.byref(scale)), "pl_qam_check")
+    return int(S.value), float(scale.value)
+
+
+def qam_modulate(m: int, E: int, e: "torch.Tensor", x: "torch.Tensor", stream=None):
+    """pl_qam_modulate: e uint8 [B, >= E], x float64 [B, >= 2 S]: device tensors, unit inner stride, any row pitch."""
+    check(lib.pl_qam_modulate(int(m), int(E), e.shape[0], e.data_ptr(), _ld(e), x.data_ptr(), _ld(x), _stream(stream)),
+          "pl_qam_modulate")
+
+
+def qam_awgn(m: int, E: int, e: "torch.Tensor | None", snr_db: float, seed: int, frame_offset: int, y: "torch.Tensor",
+             stream=None):
+    """pl_qam_awgn: e uint8 [B, >= E] or None (all-zero bits), y float64 [B, >= 2 S] on the device."""
+    check(lib.pl_qam_awgn(int(m), int(E), y.shape[0], None if e is None else e.data_ptr(), 0 if e is None else _ld(e),
+                          float(snr_db), ctypes.c_uint64(seed & (2**64 - 1)), int(frame_offset), y.data_ptr(), _ld(y),
+                          _stream(stream)), "pl_qam_awgn")
+
+
+def qam_demap(m: int, E: int, y: "torch.Tensor", snr_db: float, llr: "torch.Tensor", stream=None):
+    """pl_qam_demap: y float64 [B, >= 2 S], llr float64 or float32 [B, >= E] on the device."""
+    check(lib.pl_qam_demap(int(m), int(E), y.shape[0], y.data_ptr(), _ld(y), float(snr_db), llr.data_ptr(), _ld(llr),
+                           PL_QAM_LLR_F32 if llr.dtype == torch.float32 else 0, _stream(stream)), "pl_qam_demap")
 
 
 def random_bits(seed: int, frame_offset: int, bits: "torch.Tensor", stream=None):

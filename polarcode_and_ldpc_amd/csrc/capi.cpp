@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "internal.hpp"
+#include "qam_check.hpp"
 
 // Device workspace of one stream (polar: per resident wavefront; LDPC codes
 // whose messages exceed LDS: per frame of a chunk).  Grown lazily to the batch.
@@ -1402,6 +1403,74 @@ extern "C" int pl_polar_rate_recover(const pl_polar_rm* in, const void* llr, int
     const hipError_t err = pl::polar_rate_recover_launch(rm, llr, ld_llr, flags & PL_PRM_LLR_F32, batch, out, ld_out,
                                                          known_llr, flags & PL_PRM_ACCUMULATE, (hipStream_t)stream);
     return err == hipSuccess ? PL_OK : hipfail(err, "polar rate recover launch");
+}
+
+// ---- Gray-mapped QAM (qam.hip); the definition: include/polarldpc.h, pl_qam_check ----
+extern "C" int pl_qam_check(int32_t m, int64_t E, int64_t* S, double* scale) {
+    const pl::QamStatus st = pl::qam_check(m, E, S, scale);
+    return st.code ? fail(st.code, st.msg) : PL_OK;
+}
+
+// what the three entry points share, every check before the first device call
+static int qam_args(int32_t m, int64_t E, int64_t batch, int64_t* S, double* scale) {
+    if (int rc = pl_qam_check(m, E, S, scale)) return rc;
+    if (batch < 0) return fail(PL_EINVAL, "batch must be >= 0");
+    return PL_OK;
+}
+
+// sigma of an Es/N0 in dB, the expression order of pl_awgn_llr
+static int qam_sigma(double snr_db, double* sigma) {
+    if (!std::isfinite(snr_db)) return fail(PL_EINVAL, "snr_db must be finite");
+    const double snr_linear = std::pow(10.0, snr_db / 10.0);
+    *sigma = std::sqrt(1.0 / (2.0 * snr_linear));
+    return PL_OK;
+}
+
+extern "C" int pl_qam_modulate(int32_t m, int64_t E, int64_t batch, const uint8_t* e, int64_t ld_e, double* x,
+                               int64_t ld_x, void* stream) {
+    int64_t S;
+    double scale;
+    if (int rc = qam_args(m, E, batch, &S, &scale)) return rc;
+    if (batch > 0 && (!e || !x)) return fail(PL_EINVAL, "device pointers must not be NULL");
+    if ((uintptr_t)x & 7) return fail(PL_EINVAL, "x_dev must be aligned to its element type");
+    if (ld_e < E) return fail(PL_EINVAL, "ld_e < E = " + std::to_string(E));
+    if (ld_x < 2 * S) return fail(PL_EINVAL, "ld_x < 2 S = " + std::to_string(2 * S));
+    const hipError_t err = pl::qam_modulate_launch(m, E, S, scale, e, ld_e, batch, x, ld_x, (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "qam modulate launch");
+}
+
+extern "C" int pl_qam_awgn(int32_t m, int64_t E, int64_t batch, const uint8_t* e, int64_t ld_e, double snr_db,
+                           uint64_t seed, int64_t frame_offset, double* y, int64_t ld_y, void* stream) {
+    int64_t S;
+    double scale, sigma;
+    if (int rc = qam_args(m, E, batch, &S, &scale)) return rc;
+    if (batch > 0 && !y) return fail(PL_EINVAL, "y_dev must not be NULL");
+    if (int rc = qam_sigma(snr_db, &sigma)) return rc;
+    if ((uintptr_t)y & 7) return fail(PL_EINVAL, "y_dev must be aligned to its element type");
+    if (e && ld_e < E) return fail(PL_EINVAL, "ld_e < E = " + std::to_string(E));
+    if (ld_y < 2 * S) return fail(PL_EINVAL, "ld_y < 2 S = " + std::to_string(2 * S));
+    const hipError_t err = pl::qam_awgn_launch(m, E, S, scale, e, ld_e, batch, sigma, seed, frame_offset, y, ld_y,
+                                               (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "qam awgn launch");
+}
+
+extern "C" int pl_qam_demap(int32_t m, int64_t E, int64_t batch, const double* y, int64_t ld_y, double snr_db,
+                            void* llr, int64_t ld_llr, int32_t flags, void* stream) {
+    int64_t S;
+    double scale, sigma;
+    if (int rc = qam_args(m, E, batch, &S, &scale)) return rc;
+    if (batch > 0 && (!y || !llr)) return fail(PL_EINVAL, "device pointers must not be NULL");
+    if (flags & ~PL_QAM_LLR_F32) return fail(PL_EINVAL, "unknown flag bits");
+    if (int rc = qam_sigma(snr_db, &sigma)) return rc;
+    if (((uintptr_t)y & 7) || ((uintptr_t)llr & ((flags & PL_QAM_LLR_F32) ? 3 : 7)))
+        return fail(PL_EINVAL, "y_dev and llr_dev must be aligned to their element type");
+    if (ld_y < 2 * S) return fail(PL_EINVAL, "ld_y < 2 S = " + std::to_string(2 * S));
+    if (ld_llr < E) return fail(PL_EINVAL, "ld_llr < E = " + std::to_string(E));
+    const double s2 = sigma * sigma;
+    const double w = 1.0 / (2.0 * s2);
+    const hipError_t err = pl::qam_demap_launch(m, E, S, scale, y, ld_y, batch, w, llr, ld_llr, flags & PL_QAM_LLR_F32,
+                                                (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "qam demap launch");
 }
 
 extern "C" int pl_count_errors(const uint8_t* ref, int64_t ldr, const uint8_t* dec, int64_t ldd, int32_t width,

@@ -192,19 +192,6 @@ __global__ void awgn_kernel(const uint8_t* __restrict__ cw, int n, int64_t batch
     }
 }
 
-PL_DEV void normal_pair(uint64_t seed, uint32_t salt, uint32_t ctr, uint64_t f, double& z0, double& z1) {
-    const pl_u4 r = philox4x32_10(pl_u4{ctr, (uint32_t)f, (uint32_t)(f >> 32), salt}, (uint32_t)seed ^ 0x5bd1e995u,
-                                  (uint32_t)(seed >> 32));
-    const uint64_t a = ((uint64_t)r.y << 32) | r.x, c = ((uint64_t)r.w << 32) | r.z;
-    const double u1 = ((double)(a >> 11) + 1.0) * 0x1.0p-53;
-    const double u2 = (double)(c >> 11) * 0x1.0p-53;
-    const double rad = sqrt(-2.0 * log(u1));
-    double sn, cs;
-    sincospi(2.0 * u2, &sn, &cs);
-    z0 = rad * cs;
-    z1 = rad * sn;
-}
-
 // Rayleigh block-free fading (src/channel/fading.py:31-63): per bit h = |h_r + i h_i|,
 // h_r, h_i ~ N(0, 1/2); y = h s + N(0, sigma); LLR = 2 y h / sigma^2 (CSI at the
 // receiver).  One thread per bit, Philox keyed by (seed, global frame, bit).

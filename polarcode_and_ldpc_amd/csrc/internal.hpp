@@ -179,4 +179,15 @@ hipError_t polar_rate_match_launch(const pl_polar_rm& rm, const uint8_t* cw, int
 hipError_t polar_rate_recover_launch(const pl_polar_rm& rm, const void* llr, int64_t ldl, bool llr_f32, int64_t batch,
                                      double* out, int64_t ldo, double known, bool acc, hipStream_t s);
 
+// ---- Gray-mapped QAM (qam.hip); the definition: include/polarldpc.h, pl_qam_check ----
+// m, E checked (qam_check), S and scale from it.  e uint8 [batch][lde] (null for awgn: all-zero bits); x, y
+// double [batch][ld] of 2 S used elements; llr [batch][ldl] double or float; pitches in elements; w = 1 / (2
+// sigma^2).  All chunk their launches themselves.
+hipError_t qam_modulate_launch(int m, int64_t E, int64_t S, double scale, const uint8_t* e, int64_t lde, int64_t batch,
+                               double* x, int64_t ldx, hipStream_t s);
+hipError_t qam_awgn_launch(int m, int64_t E, int64_t S, double scale, const uint8_t* e, int64_t lde, int64_t batch,
+                           double sigma, uint64_t seed, int64_t off, double* y, int64_t ldy, hipStream_t s);
+hipError_t qam_demap_launch(int m, int64_t E, int64_t S, double scale, const double* y, int64_t ldy, int64_t batch,
+                            double w, void* llr, int64_t ldl, bool llr_f32, hipStream_t s);
+
 }  // namespace pl

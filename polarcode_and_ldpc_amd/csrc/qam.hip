@@ -1,0 +1,253 @@
+// Gray-mapped square QAM on gfx950 (MI355X): modulator, complex AWGN, max-log soft demapper.
+// The definition (bit to axis, the Gray axis mapping, the scale, the symbol layout, the noise stream and
+// the demapper's operation order): include/polarldpc.h at pl_qam_check.  H = m / 2 bits per axis is a
+// template parameter, so every loop over bits and levels unrolls and every value stays in a register.
+// Mapping of the two transmit kernels: one thread a symbol, symbol-major within a row: a thread reads its
+// m codeword bytes (zeros behind E) and writes I and Q, as one 16-byte store where the address allows.
+//   qam_tx_kernel<H, NOISE>: NOISE adds sigma z of the symbol's Box-Muller pair (common.hpp normal_pair,
+//     salt kQamSalt, counter s): one Philox call, one log, one sqrt and one sincospi per symbol.
+// The demapper is output-driven, as the rate matchers are (polar_ratematch.hip's piece scheme):
+//   qam_demap_kernel<H, T>: one thread a group of G symbols, V = G m LLRs; G = 2 for float with m = 2, 6
+//     and 1 otherwise, so that V sizeof(T) is a multiple of 16 bytes and every group of a row meets the
+//     16-byte boundaries of the output at the same offset `head`.  Per axis the 2^H squared distances are
+//     computed once and each of the H bits takes its two minima over them (the level sets are compile-time
+//     masks).  A whole group goes out as `head` single elements, 16-byte stores, and the rest as single
+//     elements; the group cut by the row's end goes out element by element.
+// Launches stay below 2^31 work-items (row chunks), so work-item indices are 32-bit.
+#include "common.hpp"
+#include "internal.hpp"
+
+namespace pl {
+
+constexpr unsigned kQamThreads = 256;
+constexpr int64_t kQamMaxItems = ((int64_t)1 << 31) - kQamThreads;
+constexpr uint32_t kQamSalt = 0x9A3A9A3Au;
+
+// integer level of the H axis bits b[0], b[1], ...: c_p = c_(p-1) ^ b_p, idx = sum c_p 2^(H-1-p), a = 2^H - 1 - 2 idx
+template <int H>
+PL_DEV int qam_level(const uint32_t (&b)[H]) {
+    uint32_t c = 0, idx = 0;
+#pragma unroll
+    for (int p = 0; p < H; ++p) {
+        c ^= b[p];
+        idx = (idx << 1) | c;
+    }
+    return ((1 << H) - 1) - 2 * (int)idx;
+}
+
+template <int H, bool NOISE>
+__global__ void __launch_bounds__(kQamThreads)
+qam_tx_kernel(const uint8_t* __restrict__ e, int64_t lde, uint32_t E, uint32_t S, uint32_t total, double scale,
+              double sigma, uint64_t seed, uint64_t f0, double* __restrict__ out, int64_t ldo) {
+    constexpr uint32_t M = 2 * H;
+    const uint32_t idx = blockIdx.x * kQamThreads + threadIdx.x;
+    if (idx >= total) return;
+    const uint32_t row = idx / S, s = idx - row * S;
+    uint32_t bi[H] = {}, bq[H] = {};
+    if (e) {
+        const uint8_t* src = e + (int64_t)row * lde;
+        const uint32_t t0 = s * M;  // < E <= 2^30
+#pragma unroll
+        for (int p = 0; p < H; ++p) {
+            bi[p] = t0 + 2 * p < E ? src[t0 + 2 * p] & 1u : 0u;
+            bq[p] = t0 + 2 * p + 1 < E ? src[t0 + 2 * p + 1] & 1u : 0u;
+        }
+    }
+    double vi = (double)qam_level<H>(bi) * scale, vq = (double)qam_level<H>(bq) * scale;
+    if (NOISE) {
+        double z0, z1;
+        normal_pair(seed, kQamSalt, s, f0 + row, z0, z1);
+        vi = vi + sigma * z0;
+        vq = vq + sigma * z1;
+    }
+    double* o = out + (int64_t)row * ldo + 2 * (int64_t)s;
+    if (((uintptr_t)o & 15u) == 0) {
+        *reinterpret_cast<double2*>(o) = make_double2(vi, vq);
+    } else {
+        o[0] = vi;
+        o[1] = vq;
+    }
+}
+
+// the H LLRs of one axis value r: llr[p] = (min d over levels with bit p = 1  -  min d over levels with bit p = 0) w
+template <int H>
+PL_DEV void qam_axis_llr(double r, double scale, double w, double (&llr)[H]) {
+    constexpr int L = 1 << H;
+    double d[L];
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+        const double t = r - (double)((L - 1) - 2 * i) * scale;
+        d[i] = t * t;
+    }
+#pragma unroll
+    for (int p = 0; p < H; ++p) {
+        // bit p of level index i: c_p ^ c_(p-1) = bit H-1-p of i ^ (i >> 1); index 0 has every bit 0 and
+        // index 2^(H-1-p) has bit p = 1.  Every d is NaN or none is, so the order of the minima is free.
+        double d0 = d[0], d1 = d[1 << (H - 1 - p)];
+#pragma unroll
+        for (int i = 1; i < L; ++i) {
+            if (((i ^ (i >> 1)) >> (H - 1 - p)) & 1) {
+                if (i != (1 << (H - 1 - p))) d1 = __builtin_fmin(d1, d[i]);
+            } else {
+                d0 = __builtin_fmin(d0, d[i]);
+            }
+        }
+        llr[p] = (d1 - d0) * w;
+    }
+}
+
+// v[0:V) to o[0:V), V sizeof(T) a multiple of 16 and o + HEAD on a 16-byte boundary
+template <int HEAD, int V, typename T>
+PL_DEV void qam_store_group(T* o, const T (&v)[V]) {
+    constexpr int EPT = 16 / sizeof(T);
+#pragma unroll
+    for (int j = 0; j < HEAD; ++j) o[j] = v[j];
+#pragma unroll
+    for (int q = HEAD; q + EPT <= V; q += EPT) {
+        union { uint4 u; T t[EPT]; } x;
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) x.t[j] = v[q + j];
+        *reinterpret_cast<uint4*>(o + q) = x.u;
+    }
+    if (HEAD > 0) {
+#pragma unroll
+        for (int j = V - (EPT - HEAD); j < V; ++j) o[j] = v[j];
+    }
+}
+
+template <int H, typename T>
+__global__ void __launch_bounds__(kQamThreads)
+qam_demap_kernel(const double* __restrict__ y, int64_t ldy, uint32_t E, uint32_t S, uint32_t W, uint32_t total,
+                 double scale, double w, T* __restrict__ llr, int64_t ldl) {
+    constexpr uint32_t M = 2 * H;
+    constexpr uint32_t G = (sizeof(T) == 4 && (H & 1)) ? 2 : 1;
+    constexpr uint32_t V = G * M;
+    constexpr uint32_t EPT = 16 / sizeof(T);
+    static_assert(V % EPT == 0, "a group is whole 16-byte pieces");
+    const uint32_t idx = blockIdx.x * kQamThreads + threadIdx.x;
+    if (idx >= total) return;
+    const uint32_t row = idx / W, g = idx - row * W;
+    const double* src = y + (int64_t)row * ldy;
+    T v[V];
+#pragma unroll
+    for (uint32_t k = 0; k < G; ++k) {
+        const uint32_t s = g * G + k;
+        double ri = 0.0, rq = 0.0;
+        if (s < S) {
+            const double* ps = src + 2 * (int64_t)s;
+            if (((uintptr_t)ps & 15u) == 0) {
+                const double2 pr = *reinterpret_cast<const double2*>(ps);
+                ri = pr.x;
+                rq = pr.y;
+            } else {
+                ri = ps[0];
+                rq = ps[1];
+            }
+        }
+        double li[H], lq[H];
+        qam_axis_llr<H>(ri, scale, w, li);
+        qam_axis_llr<H>(rq, scale, w, lq);
+#pragma unroll
+        for (int p = 0; p < H; ++p) {
+            v[k * M + 2 * p] = (T)li[p];
+            v[k * M + 2 * p + 1] = (T)lq[p];
+        }
+    }
+    const uint32_t t0 = g * V;  // < E: W = ceil(E / V)
+    T* o = llr + (int64_t)row * ldl + t0;
+    if (E - t0 >= V) {
+        const uint32_t head = ((uint32_t)(-(uintptr_t)o) & 15u) / (uint32_t)sizeof(T);
+        if (head == 0) {
+            qam_store_group<0, V, T>(o, v);
+        } else if constexpr (EPT == 2) {
+            qam_store_group<1, V, T>(o, v);
+        } else {
+            if (head == 1) qam_store_group<1, V, T>(o, v);
+            else if (head == 2) qam_store_group<2, V, T>(o, v);
+            else qam_store_group<3, V, T>(o, v);
+        }
+    } else {
+#pragma unroll
+        for (uint32_t j = 0; j < V; ++j)
+            if (j < E - t0) o[j] = v[j];
+    }
+}
+
+// rows of W work-items each, in launches below 2^31 work-items; fn(first row, work-items)
+template <class Launch>
+static hipError_t qam_chunks(int64_t batch, int64_t W, Launch fn) {
+    const int64_t step = kQamMaxItems / W;  // W <= 2^29: at least 3 rows
+    for (int64_t b0 = 0; b0 < batch; b0 += step) {
+        const int64_t rows = batch - b0 < step ? batch - b0 : step;
+        const hipError_t e = fn(b0, (uint32_t)(rows * W));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+template <int H, bool NOISE>
+static hipError_t qam_tx(const uint8_t* e, int64_t lde, int64_t E, int64_t S, int64_t batch, double scale,
+                         double sigma, uint64_t seed, int64_t off, double* out, int64_t ldo, hipStream_t st) {
+    return qam_chunks(batch, S, [&](int64_t b0, uint32_t total) {
+        hipLaunchKernelGGL((qam_tx_kernel<H, NOISE>), dim3((total + kQamThreads - 1) / kQamThreads), dim3(kQamThreads),
+                           0, st, e ? e + b0 * lde : e, lde, (uint32_t)E, (uint32_t)S, total, scale, sigma, seed,
+                           (uint64_t)(off + b0), out + b0 * ldo, ldo);
+        return hipGetLastError();
+    });
+}
+
+template <bool NOISE>
+static hipError_t qam_tx_m(int m, const uint8_t* e, int64_t lde, int64_t E, int64_t S, int64_t batch, double scale,
+                           double sigma, uint64_t seed, int64_t off, double* out, int64_t ldo, hipStream_t st) {
+    switch (m) {
+        case 2: return qam_tx<1, NOISE>(e, lde, E, S, batch, scale, sigma, seed, off, out, ldo, st);
+        case 4: return qam_tx<2, NOISE>(e, lde, E, S, batch, scale, sigma, seed, off, out, ldo, st);
+        case 6: return qam_tx<3, NOISE>(e, lde, E, S, batch, scale, sigma, seed, off, out, ldo, st);
+        default: return qam_tx<4, NOISE>(e, lde, E, S, batch, scale, sigma, seed, off, out, ldo, st);
+    }
+}
+
+hipError_t qam_modulate_launch(int m, int64_t E, int64_t S, double scale, const uint8_t* e, int64_t lde, int64_t batch,
+                               double* x, int64_t ldx, hipStream_t s) {
+    if (batch == 0) return hipSuccess;
+    return qam_tx_m<false>(m, e, lde, E, S, batch, scale, 0.0, 0, 0, x, ldx, s);
+}
+
+hipError_t qam_awgn_launch(int m, int64_t E, int64_t S, double scale, const uint8_t* e, int64_t lde, int64_t batch,
+                           double sigma, uint64_t seed, int64_t off, double* y, int64_t ldy, hipStream_t s) {
+    if (batch == 0) return hipSuccess;
+    return qam_tx_m<true>(m, e, lde, E, S, batch, scale, sigma, seed, off, y, ldy, s);
+}
+
+template <int H, typename T>
+static hipError_t qam_demap(int64_t E, int64_t S, double scale, const double* y, int64_t ldy, int64_t batch, double w,
+                            T* llr, int64_t ldl, hipStream_t st) {
+    constexpr int64_t V = ((sizeof(T) == 4 && (H & 1)) ? 2 : 1) * 2 * H;
+    const int64_t W = (E + V - 1) / V;
+    return qam_chunks(batch, W, [&](int64_t b0, uint32_t total) {
+        hipLaunchKernelGGL((qam_demap_kernel<H, T>), dim3((total + kQamThreads - 1) / kQamThreads), dim3(kQamThreads), 0,
+                           st, y + b0 * ldy, ldy, (uint32_t)E, (uint32_t)S, (uint32_t)W, total, scale, w,
+                           llr + b0 * ldl, ldl);
+        return hipGetLastError();
+    });
+}
+
+template <typename T>
+static hipError_t qam_demap_m(int m, int64_t E, int64_t S, double scale, const double* y, int64_t ldy, int64_t batch,
+                              double w, T* llr, int64_t ldl, hipStream_t st) {
+    switch (m) {
+        case 2: return qam_demap<1, T>(E, S, scale, y, ldy, batch, w, llr, ldl, st);
+        case 4: return qam_demap<2, T>(E, S, scale, y, ldy, batch, w, llr, ldl, st);
+        case 6: return qam_demap<3, T>(E, S, scale, y, ldy, batch, w, llr, ldl, st);
+        default: return qam_demap<4, T>(E, S, scale, y, ldy, batch, w, llr, ldl, st);
+    }
+}
+
+hipError_t qam_demap_launch(int m, int64_t E, int64_t S, double scale, const double* y, int64_t ldy, int64_t batch,
+                            double w, void* llr, int64_t ldl, bool llr_f32, hipStream_t s) {
+    if (batch == 0) return hipSuccess;
+    return llr_f32 ? qam_demap_m(m, E, S, scale, y, ldy, batch, w, (float*)llr, ldl, s)
+                   : qam_demap_m(m, E, S, scale, y, ldy, batch, w, (double*)llr, ldl, s);
+}
+
+}  // namespace pl

@@ -50,7 +50,7 @@ def _log(log_path, mc, **key):
 
 def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: int, config: Dict,
                    list_size: int = 0, crc_polynomial: Optional[str] = None, batch: int = 65536, seed: int = 0,
-                   group=None, log_path=None, rate_match=None):
+                   group=None, log_path=None, rate_match=None, modulation=None):
     """ber_simulation.py:132-198 -> (ber, fer, points).  list_size 0 = SC (the
     reference), >= 1 = SCL, with crc_polynomial = CA-SCL (CRC inside the K bits).
     log_path: JSON-lines file of finished points; a rerun resumes from it.
@@ -61,7 +61,11 @@ def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: i
     frozen set is config["frozen_bits"] when present, else
     construct_rate_matched(K, matcher) at its default design SNR.  E, mode, the
     permutation and known_llr enter the log's run key only when rate matching is
-    used."""
+    used.
+
+    modulation: None (BPSK), or a channel.QAMModem: the transmitted bits cross the
+    channel as Gray-mapped QAM symbols (polar_round_fn's modulation) and snr_db is
+    Es/N0 per QAM symbol; its bits per symbol enter the run key only when given."""
     import torch
     from ..lib_wrappers import PolarLibWrapper
     from ..polar.decoder import CASCLDecoder, SCDecoder, SCLDecoder
@@ -75,13 +79,17 @@ def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: i
         more = dict(E=rm.E, mode=rm.mode, perm=rm.perm.tolist(), known_llr=rm.known_llr)
     else:
         fr = PolarLibWrapper(N, K, 2.0).get_frozen_bits_positions()
+    kw = {}
+    if modulation is not None:
+        more = dict(more, modulation=modulation.m)
+        kw["modulation"] = modulation
     if list_size <= 0:
         dec = SCDecoder(N, K, frozen_bits=fr)
     elif crc_polynomial:
         dec = CASCLDecoder(N, K, list_size, frozen_bits=fr, crc_polynomial=crc_polynomial)
     else:
         dec = SCLDecoder(N, K, list_size, frozen_bits=fr)
-    mc = MonteCarlo(polar_round_fn(dec, seed=seed, crc_polynomial=crc_polynomial, rate_matcher=rm), info_bits=K,
+    mc = MonteCarlo(polar_round_fn(dec, seed=seed, crc_polynomial=crc_polynomial, rate_matcher=rm, **kw), info_bits=K,
                     batch=batch, group=group, device=torch.device("cuda", torch.cuda.current_device()))
     log = _log(log_path, mc, code="polar", N=N, K=K, list_size=list_size, crc=crc_polynomial, frames=num_frames,
                max_errors=max_errors, seed=seed, frozen=_digest(np.sort(np.asarray(fr))), **more)
@@ -116,7 +124,7 @@ def simulate_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: in
 def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: int, base, Z: int,
                      max_iter: int = 20, normalization: float = 0.75, dtype=np.float64, batch: int = 65536,
                      seed: int = 0, group=None, random_codewords: bool = False, log_path=None, rate_match=None,
-                     fixed=None):
+                     fixed=None, modulation=None):
     """simulate_ldpc for the quasi-cyclic code (base, Z): QCLayeredMSDecoder (layered
     normalised min-sum, early stop, state in `dtype`) on frames of the all-zero
     codeword or, random_codewords, of random messages encoded on the device from
@@ -132,7 +140,11 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
     fixed: None, or (llr_scale, llr_max, msg_max): the int8 fixed-point decoder
     QCFixedMSDecoder with these parameters instead (`dtype` is not used; the
     channel LLRs stay fp64 and the decoder quantises them).  The three values
-    enter the log's run key, as "fixed", only when given."""
+    enter the log's run key, as "fixed", only when given.
+
+    modulation: None (BPSK), or a channel.QAMModem (ldpc_round_fn's modulation; it needs
+    random_codewords); snr_db is then Es/N0 per QAM symbol, and its bits per symbol enter the
+    run key."""
     import torch
     from ..ldpc.decoder import QCFixedMSDecoder, QCLayeredMSDecoder
     from ..ldpc.encoder import QCLDPCEncoder
@@ -141,6 +153,10 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
     if fixed is not None:
         fixed = (float(fixed[0]), int(fixed[1]), int(fixed[2]))
         more["fixed"] = list(fixed)
+    kw = {}
+    if modulation is not None:
+        more["modulation"] = modulation.m
+        kw["modulation"] = modulation
 
     def make_decoder(b):
         if fixed is None:
@@ -156,7 +172,7 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
         dec = make_decoder(rm.decoder_base())
         k = rm.k - rm.fillers
         enc = QCLDPCEncoder(base, Z) if random_codewords else None
-        mc = MonteCarlo(ldpc_round_fn(dec, seed=seed, encoder=enc, rate_matcher=rm), info_bits=k, batch=batch,
+        mc = MonteCarlo(ldpc_round_fn(dec, seed=seed, encoder=enc, rate_matcher=rm, **kw), info_bits=k, batch=batch,
                         group=group, device=torch.device("cuda", torch.cuda.current_device()))
         log = _log(log_path, mc, code="qcldpc", n=rm.n, k=k, Z=int(Z), max_iter=max_iter, norm=float(normalization),
                    dtype=dtype_name(dec), random=random_codewords, frames=num_frames, max_errors=max_errors,
@@ -167,7 +183,7 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
     dec = make_decoder(base)
     k = dec.n - dec.m
     enc = QCLDPCEncoder(base, Z) if random_codewords else None
-    mc = MonteCarlo(ldpc_round_fn(dec, seed=seed, info_bits=k, encoder=enc), info_bits=k, batch=batch, group=group,
+    mc = MonteCarlo(ldpc_round_fn(dec, seed=seed, info_bits=k, encoder=enc, **kw), info_bits=k, batch=batch, group=group,
                     device=torch.device("cuda", torch.cuda.current_device()))
     log = _log(log_path, mc, code="qcldpc", n=dec.n, k=k, Z=int(Z), max_iter=max_iter, norm=float(normalization),
                dtype=dtype_name(dec), random=random_codewords, frames=num_frames, max_errors=max_errors,
@@ -244,6 +260,9 @@ def main(argv=None):
     ap.add_argument("--fixed", default=None,
                     help="--code qcldpc: scale,llr_max,msg_max, the int8 fixed-point decoder (ldpc.QCFixedMSDecoder) "
                          "instead of the floating one; --dtype is then not used")
+    ap.add_argument("--modulation", choices=["qpsk", "16qam", "64qam", "256qam"], default=None,
+                    help="--code polar, qcldpc: Gray-mapped QAM (channel.QAMModem) instead of BPSK; --snr is then Es/N0 "
+                         "per QAM symbol; qcldpc needs --ldpc-codewords random")
     ap.add_argument("--norm", type=float, default=0.75, help="--code qcldpc: min-sum normalisation")
     ap.add_argument("--seed", type=int, default=0, help="--code qcldpc: seed of the frame source")
     ap.add_argument("--cpu-stub", action="store_true",
@@ -260,6 +279,12 @@ def main(argv=None):
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     snr = _parse_range(a.snr)
+    mod = {}
+    if a.modulation is not None and not a.cpu_stub:
+        if a.code == "ldpc":
+            ap.error("--modulation goes with --code polar or qcldpc")
+        from ..channel.qam import NAMES, QAMModem
+        mod["modulation"] = QAMModem(NAMES[a.modulation])
     if a.cpu_stub:
         from .montecarlo import stub_round_fn
         mc = MonteCarlo(stub_round_fn(seed=7, info_bits=a.K), info_bits=a.K, batch=a.batch)
@@ -274,7 +299,7 @@ def main(argv=None):
                 ap.error("--polar-rm takes E,mode[,p0,p1,...] with mode puncture or shorten")
             more["rate_match"] = dict(E=int(f[0]), mode=f[1], sub_blocks=[int(x) for x in f[2:]] or None)
         ber, fer, pts = simulate_polar(snr, a.frames, a.max_errors, {"encoding": {"N": a.N, "K": a.K}},
-                                       a.list_size, a.crc, a.batch, log_path=a.log, **more)
+                                       a.list_size, a.crc, a.batch, log_path=a.log, **more, **mod)
     elif a.code == "qcldpc":
         from ..ldpc.matrix import qc_encodable_base
         q = [int(x) for x in a.qc.split(",")]
@@ -295,7 +320,7 @@ def main(argv=None):
         ber, fer, pts = simulate_qc_ldpc(snr, a.frames, a.max_errors, base, q[2], max_iter=a.max_iter,
                                          normalization=a.norm, dtype=np.dtype(a.dtype).type, batch=a.batch,
                                          seed=a.seed, random_codewords=a.ldpc_codewords == "random", log_path=a.log,
-                                         **more)
+                                         **more, **mod)
     else:
         ber, fer, pts = simulate_ldpc(snr, a.frames, a.max_errors,
                                       {"encoding": {"n": a.n, "k": a.k}, "decoding": {"max_iterations": a.max_iter}},

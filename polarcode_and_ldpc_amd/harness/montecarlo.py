@@ -223,7 +223,20 @@ def _polar_messages(msg, s, offset, K, crc_polynomial):
         _native.crc_append(msg, K - L, L, CRC_POLYNOMIALS[name])
 
 
-def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm):
+def _qam_channel(modem, bits, E, nframes, snr_db, seed, offset, bufs, rx):
+    """The chains' channel with a channel.QAMModem: the E transmitted bits of each frame through modem.awgn
+    (seed and frame offset as the BPSK call's) and modem.demap into rx [nframes, E], whose dtype the next
+    stage reads.  The symbols live in bufs["sym"]."""
+    import torch
+    S2 = 2 * modem.S(E)
+    if "sym" not in bufs or bufs["sym"].shape[0] < nframes:
+        bufs["sym"] = torch.empty((nframes, S2), dtype=torch.float64, device="cuda")
+    sym = bufs["sym"][:nframes]
+    modem.awgn(bits, E, nframes, snr_db, seed, frame_offset=offset, out=sym)
+    modem.demap(sym, E, snr_db, out=rx)
+
+
+def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm, modem=None):
     """polar_round_fn's rate-matched chain; see there."""
     import torch
     from .. import _native
@@ -246,7 +259,10 @@ def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm):
         _polar_messages(msg, s, offset, K, crc_polynomial)
         _native.polar_encode(decoder.plan, msg, cw)
         rm.select(cw, out=tx)
-        AWGNChannel(snr_db).llr_batch_device(tx, E, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=rx)
+        if modem is None:
+            AWGNChannel(snr_db).llr_batch_device(tx, E, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=rx)
+        else:
+            _qam_channel(modem, tx, E, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, rx)
         rm.recover(rx, out=llr)
         decoder.plan.decode(llr, out)
         counts = torch.zeros(3, dtype=torch.int64, device="cuda")
@@ -256,7 +272,7 @@ def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm):
     return fn
 
 
-def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None, rate_matcher=None):
+def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None, rate_matcher=None, modulation=None):
     """Round function for a drop-in SC/SCL decoder (polar.SCDecoder/SCLDecoder).
     Random K-bit messages (CRC appended when crc_polynomial is given, as
     src/polar/encoder.py:74-78 does), device polar encoder, device AWGN,
@@ -268,9 +284,14 @@ def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None,
     to N fp64 LLRs, decode, count.  snr_db is per transmitted symbol (Es/N0), as
     in the LDPC chain: a repeated bit collects the energy of each copy.  The
     decoder's frozen set must contain rate_matcher.forced_frozen()
-    (check_frozen; polar.construct_rate_matched builds one)."""
+    (check_frozen; polar.construct_rate_matched builds one).
+
+    modulation = a channel.QAMModem: the transmitted bits (the matcher's E, or the
+    whole codeword) cross the channel as Gray-mapped QAM symbols, modem.awgn then
+    modem.demap (max-log, fp64), with the seed derivation of the BPSK call; snr_db
+    is then Es/N0 per QAM symbol.  None: BPSK, every call as before."""
     if rate_matcher is not None:
-        return _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rate_matcher)
+        return _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rate_matcher, modulation)
     import torch
     from .. import _native
     from ..channel.awgn import AWGNChannel
@@ -294,7 +315,10 @@ def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None,
             _native.random_bits(s, offset, msg)
             _native.crc_append(msg, K - L, L, CRC_POLYNOMIALS[name])
         _native.polar_encode(decoder.plan, msg, cw)
-        AWGNChannel(snr_db).llr_batch_device(cw, N, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=llr)
+        if modulation is None:
+            AWGNChannel(snr_db).llr_batch_device(cw, N, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=llr)
+        else:
+            _qam_channel(modulation, cw, N, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, llr)
         decoder.plan.decode(llr, out)
         counts = torch.zeros(3, dtype=torch.int64, device="cuda")
         _native.count_errors(msg, out, K, counts)
@@ -311,7 +335,7 @@ def _plan_decode(decoder, llr, out, its):
     decoder.plan.decode(llr, out, its)
 
 
-def _rate_matched_round_fn(decoder, seed, encoder, rm):
+def _rate_matched_round_fn(decoder, seed, encoder, rm, modem=None):
     """ldpc_round_fn's rate-matched chain; see there."""
     import torch
     from .. import _native
@@ -327,7 +351,8 @@ def _rate_matched_round_fn(decoder, seed, encoder, rm):
 
     def fn(snr_index, snr_db, offset, nframes):
         if bufs.get("B", 0) < nframes:
-            bufs.update(B=nframes, rx=torch.empty((nframes, E), dtype=torch.float64, device="cuda"),
+            bufs.update(B=nframes, rx=torch.empty((nframes, E), dtype=torch.float64 if modem is None else ftype,
+                                                  device="cuda"),
                         llr=torch.empty((nframes, n_dec), dtype=ftype, device="cuda"),
                         out=torch.empty((nframes, n_dec), dtype=torch.uint8, device="cuda"),
                         its=torch.empty((nframes,), dtype=torch.int32, device="cuda"),
@@ -347,7 +372,10 @@ def _rate_matched_round_fn(decoder, seed, encoder, rm):
             msg[:, kf:] = 0  # the fillers are known zeros
             encoder.encode_batch_device(msg, out=cw)
             rm.select(cw, out=tx)
-            AWGNChannel(snr_db).llr_batch_device(tx, E, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=rx)
+            if modem is None:
+                AWGNChannel(snr_db).llr_batch_device(tx, E, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=rx)
+            else:
+                _qam_channel(modem, tx, E, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, rx)
             ref = msg
         rm.recover(rx, out=llr)
         _plan_decode(decoder, llr, out, its)
@@ -357,7 +385,8 @@ def _rate_matched_round_fn(decoder, seed, encoder, rm):
     return fn
 
 
-def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encoder=None, rate_matcher=None):
+def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encoder=None, rate_matcher=None,
+                  modulation=None):
     """Round function for BPDecoder / MSDecoder / LayeredMSDecoder (any decoder
     with `.plan`, `.n` and `.m`).  A QCFixedMSDecoder takes the same chain: the
     channel LLRs (and the recovery) stay fp64 and the decoder quantises them.
@@ -374,9 +403,19 @@ def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encod
     QCLDPCEncoder of the whole code, or None) encodes random messages whose
     filler tail is zero; then select, AWGN over E, recover into the decoder's
     dtype, decode, errors over the first k - fillers positions (`info_bits` is
-    not used).  With the all-zero codeword encode and select are skipped."""
+    not used).  With the all-zero codeword encode and select are skipped.
+
+    modulation = a channel.QAMModem: the transmitted bits cross the channel as
+    Gray-mapped QAM symbols (modem.awgn, modem.demap; polar_round_fn has the
+    details); the demapper writes fp32 for a float32 decoder, else fp64.  A QAM
+    bit channel is not symmetric -- a bit's error probability depends on the
+    other bits of its symbol -- so the all-zero codeword stands for nothing:
+    `encoder` is required.  None: BPSK, every call as before."""
+    assert modulation is None or encoder is not None, \
+        "modulation needs an encoder: the bit channels of a QAM symbol are not symmetric, so the all-zero " \
+        "codeword shortcut is invalid"
     if rate_matcher is not None:
-        return _rate_matched_round_fn(decoder, seed, encoder, rate_matcher)
+        return _rate_matched_round_fn(decoder, seed, encoder, rate_matcher, modulation)
     import torch
     from .. import _native
     from ..channel.awgn import AWGNChannel
@@ -386,11 +425,13 @@ def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encod
         info = torch.from_numpy(np.asarray(encoder.info_positions, dtype=np.int64)).cuda()
     else:
         k = info_bits if info_bits is not None else n - decoder.m
+    f32 = modulation is not None and np.dtype(getattr(decoder, "dtype", np.float64)) == np.float32
     bufs = {}
 
     def fn(snr_index, snr_db, offset, nframes):
         if bufs.get("B", 0) < nframes:
-            bufs.update(B=nframes, llr=torch.empty((nframes, n), dtype=torch.float64, device="cuda"),
+            bufs.update(B=nframes, llr=torch.empty((nframes, n), dtype=torch.float32 if f32 else torch.float64,
+                                                   device="cuda"),
                         out=torch.empty((nframes, n), dtype=torch.uint8, device="cuda"),
                         its=torch.empty((nframes,), dtype=torch.int32, device="cuda"),
                         zero=torch.zeros((nframes, n), dtype=torch.uint8, device="cuda"),
@@ -406,7 +447,10 @@ def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encod
         else:
             _native.random_bits(s, offset, msg)
             encoder.encode_batch_device(msg, out=cw)
-            AWGNChannel(snr_db).llr_batch_device(cw, n, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=llr)
+            if modulation is None:
+                AWGNChannel(snr_db).llr_batch_device(cw, n, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=llr)
+            else:
+                _qam_channel(modulation, cw, n, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, llr)
             _plan_decode(decoder, llr, out, its)
             _native.count_errors(msg, out.index_select(1, info).contiguous(), k, counts)
         return counts.cpu().numpy()
