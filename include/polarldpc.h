@@ -831,6 +831,55 @@ int pl_qam_awgn(int32_t m, int64_t E, int64_t batch, const uint8_t* e_dev, int64
 int pl_qam_demap(int32_t m, int64_t E, int64_t batch, const double* y_dev, int64_t ld_y, double snr_db, void* llr_dev,
                  int64_t ld_llr, int32_t flags, void* stream);
 
+/* ---- Bit interleaver between rate matching and the QAM modem ---------------------------
+ * The m bit positions of a QAM symbol are unequally reliable and a rate matcher hands over
+ * runs of consecutive code bits; the interleaver spreads such a run over the positions.
+ * This comment is the definition; the kernels (interleave.hip), channel.BitInterleaver and
+ * the harness cite it.  It is build-defined and given as a procedure; no standard's text
+ * or table is reproduced.
+ * An interleaver is (kind, rows, E).  It maps e[0:E) to f[0:E); its inverse acts on LLRs.
+ * Conditions; a violation is PL_EINVAL naming the first one violated, in this order:
+ *   1. kind is PL_ILV_RECT or PL_ILV_TRI
+ *   2. 1 <= E <= 2^30
+ *   3. PL_ILV_RECT: 1 <= rows <= 64.  PL_ILV_TRI: rows == 0.
+ * PL_ILV_RECT: C = ceil(E / rows).  Write e row by row into a rows x C array: cell (r, c)
+ *   holds index k = r C + c; cells with k >= E are empty.  Read column by column, c outer
+ *   and r inner, skipping empty cells.  With rows = m and E a multiple of m, bit r of
+ *   symbol s is e[r C + s].  E need not be a multiple of rows; E < rows is legal.
+ * PL_ILV_TRI: T is the smallest integer with T (T + 1) / 2 >= E.  Row i (0 .. T-1) has
+ *   T - i cells and starts at index st(i) = i T - i (i - 1) / 2.  Write e row by row; cells
+ *   with index >= E are empty (always at the tail; several trailing rows may be empty).
+ *   Read column by column: column j has rows 0 .. T-1-j; skip empty cells.
+ * pos(k) is the output position of input k: f[pos(k)] = e[k].  The deinterleaver is
+ *   e_llr[k] = f_llr[pos(k)].
+ * The device computes pos in closed form (csrc/interleave_check.hpp): no table and no device
+ * object; the kernels take the parameters by value, and each entry point checks them again
+ * itself.  pl_interleave_check and pl_interleave_index make no device call. */
+#define PL_ILV_RECT 0
+#define PL_ILV_TRI 1
+/* *dim_out (may be NULL) receives C (PL_ILV_RECT) or T (PL_ILV_TRI). */
+int pl_interleave_check(int32_t kind, int32_t rows, int64_t E, int64_t* dim_out);
+/* *pos_out = pos(k), by the code the kernels run.  PL_EINVAL for what pl_interleave_check
+ * refuses, for k outside 0 .. E-1 and for a NULL pos_out. */
+int pl_interleave_index(int32_t kind, int32_t rows, int64_t E, int64_t k, int64_t* pos_out);
+/* The largest E whose frames of elem_size bytes (1, 4, 8) the kernels permute in LDS; longer
+ * frames are permuted directly in global memory.  0 for another elem_size. */
+int64_t pl_interleave_lds_max_e(int32_t elem_size);
+/* f[b][pos(k)] = e[b][k], bytes copied whole: e_dev uint8 [batch][ld_e], f_dev uint8
+ * [batch][ld_f], pitches >= E; bytes beyond E are left alone.  Asynchronous on `stream`;
+ * batch == 0 launches nothing.  PL_EINVAL for what pl_interleave_check refuses, batch < 0, a
+ * NULL pointer with batch > 0, a short pitch, and e_dev and f_dev overlapping; every check
+ * runs before the first device call. */
+int pl_bit_interleave(int32_t kind, int32_t rows, int64_t E, int64_t batch, const uint8_t* e_dev, int64_t ld_e,
+                      uint8_t* f_dev, int64_t ld_f, void* stream);
+#define PL_ILV_LLR_F32 1 /* f_dev and e_dev are float (else double) */
+/* e[b][k] = f[b][pos(k)]: f_dev [batch][ld_f], e_dev [batch][ld_e], both double, or both
+ * float with PL_ILV_LLR_F32; pitches in elements, >= E; elements beyond E are left alone.
+ * Values are copied bit for bit (NaN payloads, -0.0).  PL_EINVAL as pl_bit_interleave, and for
+ * unknown flag bits and a pointer that is not aligned to its element type. */
+int pl_llr_deinterleave(int32_t kind, int32_t rows, int64_t E, int64_t batch, const void* f_dev, int64_t ld_f,
+                        void* e_dev, int64_t ld_e, int32_t flags, void* stream);
+
 /* Error counting (benchmarks/ber_simulation.py:180-189):
  * counts_dev[0] += bit errors, [1] += frame errors, [2] += frames, over the
  * first `width` entries of each row.  counts_dev int64[3], device. */

@@ -35,12 +35,15 @@ EXPORTS = (
     "pl_debug_ldpc_qc_fixed_plan_probe", "pl_polar_rate_match_check", "pl_debug_polar_rate_match_probe",
     "pl_polar_rate_match_forced", "pl_polar_rate_match", "pl_polar_rate_recover",
     "pl_qam_check", "pl_qam_modulate", "pl_qam_awgn", "pl_qam_demap",
+    "pl_interleave_check", "pl_interleave_index", "pl_interleave_lds_max_e", "pl_bit_interleave", "pl_llr_deinterleave",
 )
 PL_QUANT_LLR_F32 = 1  # pl_llr_quantize flag: llr_dev is float (else double)
 PL_RM_LLR_F32, PL_RM_OUT_F32, PL_RM_ACCUMULATE = 1, 2, 4  # pl_ldpc_rate_recover flags
 PL_PRM_PUNCTURE, PL_PRM_SHORTEN = 0, 1  # pl_polar_rm.mode
 PL_PRM_LLR_F32, PL_PRM_ACCUMULATE = 1, 4  # pl_polar_rate_recover flags
 PL_QAM_LLR_F32 = 1  # pl_qam_demap flag: llr_dev is float (else double)
+PL_ILV_RECT, PL_ILV_TRI = 0, 1  # the interleaver's kind
+PL_ILV_LLR_F32 = 1  # pl_llr_deinterleave flag: f_dev and e_dev are float (else double)
 
 
 class PlanInfo(ctypes.Structure):
@@ -142,6 +145,11 @@ def _load(path=LIB_PATH):
     L.pl_qam_modulate.argtypes = [I32, I64, I64, P, I64, P, I64, P]
     L.pl_qam_awgn.argtypes = [I32, I64, I64, P, I64, D, ctypes.c_uint64, I64, P, I64, P]
     L.pl_qam_demap.argtypes = [I32, I64, I64, P, I64, D, P, I64, I32, P]
+    L.pl_interleave_check.argtypes = [I32, I32, I64, ctypes.POINTER(ctypes.c_int64)]
+    L.pl_interleave_index.argtypes = [I32, I32, I64, I64, ctypes.POINTER(ctypes.c_int64)]
+    L.pl_interleave_lds_max_e.argtypes = [I32]
+    L.pl_bit_interleave.argtypes = [I32, I32, I64, I64, P, I64, P, I64, P]
+    L.pl_llr_deinterleave.argtypes = [I32, I32, I64, I64, P, I64, P, I64, I32, P]
     L.pl_ldpc_decode_soft.argtypes = [P, P, I64, I64, P, P, P, I64, P]
     L.pl_ldpc_decode_f32.argtypes = [P, P, I64, I64, P, P, P, I64, P, I64, P]
     L.pl_decode.argtypes = [P, P, I64, I64, P, P, P]
@@ -171,6 +179,7 @@ def _load(path=LIB_PATH):
     L.pl_gf2_encode.argtypes = [P, I32, I32, P, I64, I64, P, I64, P]
     for name in EXPORTS:
         getattr(L, name).restype = ctypes.c_int if name != "pl_last_error" else ctypes.c_char_p
+    L.pl_interleave_lds_max_e.restype = ctypes.c_int64
     return L
 
 
@@ -580,6 +589,38 @@ def qam_demap(m: int, E: int, y: "torch.Tensor", snr_db: float, llr: "torch.Tens
     """pl_qam_demap: y float64 [B, >= 2 S], llr float64 or float32 [B, >= E] on the device."""
     check(lib.pl_qam_demap(int(m), int(E), y.shape[0], y.data_ptr(), _ld(y), float(snr_db), llr.data_ptr(), _ld(llr),
                            PL_QAM_LLR_F32 if llr.dtype == torch.float32 else 0, _stream(stream)), "pl_qam_demap")
+
+
+# the largest E the interleaver kernels permute in LDS, by element size in bytes; longer frames go the direct way
+ILV_LDS_MAX_E = {size: int(lib.pl_interleave_lds_max_e(size)) for size in (1, 4, 8)}
+
+
+def interleave_check(kind: int, rows: int, E: int) -> int:
+    """pl_interleave_check: C (PL_ILV_RECT) or T (PL_ILV_TRI) of the interleaver (no device call).
+    AssertionError with the first violated condition."""
+    dim = ctypes.c_int64()
+    check(lib.pl_interleave_check(int(kind), int(rows), int(E), ctypes.byref(dim)), "pl_interleave_check")
+    return int(dim.value)
+
+
+def interleave_index(kind: int, rows: int, E: int, k: int) -> int:
+    """pl_interleave_index: pos(k) by the code the kernels run (no device call)."""
+    pos = ctypes.c_int64()
+    check(lib.pl_interleave_index(int(kind), int(rows), int(E), int(k), ctypes.byref(pos)), "pl_interleave_index")
+    return int(pos.value)
+
+
+def bit_interleave(kind: int, rows: int, E: int, e: "torch.Tensor", f: "torch.Tensor", stream=None):
+    """pl_bit_interleave: e, f uint8 [B, >= E]: device tensors, unit inner stride, any row pitch."""
+    check(lib.pl_bit_interleave(int(kind), int(rows), int(E), e.shape[0], e.data_ptr(), _ld(e), f.data_ptr(), _ld(f),
+                                _stream(stream)), "pl_bit_interleave")
+
+
+def llr_deinterleave(kind: int, rows: int, E: int, f: "torch.Tensor", e: "torch.Tensor", stream=None):
+    """pl_llr_deinterleave: f, e [B, >= E] on the device, both float64 or both float32."""
+    check(lib.pl_llr_deinterleave(int(kind), int(rows), int(E), f.shape[0], f.data_ptr(), _ld(f), e.data_ptr(), _ld(e),
+                                  PL_ILV_LLR_F32 if f.dtype == torch.float32 else 0, _stream(stream)),
+          "pl_llr_deinterleave")
 
 
 def random_bits(seed: int, frame_offset: int, bits: "torch.Tensor", stream=None):

@@ -1473,6 +1473,70 @@ extern "C" int pl_qam_demap(int32_t m, int64_t E, int64_t batch, const double* y
     return err == hipSuccess ? PL_OK : hipfail(err, "qam demap launch");
 }
 
+// ---- the bit interleaver (interleave.hip); the definition: include/polarldpc.h, pl_interleave_check ----
+static int ilv_args(int32_t kind, int32_t rows, int64_t E, pl::IlvParams* p) {
+    const pl::IlvStatus st = pl::ilv_check(kind, rows, E, p);
+    return st.code ? fail(st.code, st.msg) : PL_OK;
+}
+
+extern "C" int pl_interleave_check(int32_t kind, int32_t rows, int64_t E, int64_t* dim) {
+    pl::IlvParams p;
+    if (int rc = ilv_args(kind, rows, E, &p)) return rc;
+    if (dim) *dim = p.dim;
+    return PL_OK;
+}
+
+extern "C" int pl_interleave_index(int32_t kind, int32_t rows, int64_t E, int64_t k, int64_t* pos) {
+    pl::IlvParams p;
+    if (int rc = ilv_args(kind, rows, E, &p)) return rc;
+    if (k < 0 || k >= E) return fail(PL_EINVAL, "k = " + std::to_string(k) + " outside 0 .. E-1");
+    if (!pos) return fail(PL_EINVAL, "pos_out must not be NULL");
+    *pos = pl::ilv_pos(kind, p, (uint32_t)k);
+    return PL_OK;
+}
+
+extern "C" int64_t pl_interleave_lds_max_e(int32_t elem_size) {
+    return elem_size == 1 || elem_size == 4 || elem_size == 8 ? pl::kIlvLdsBytes / elem_size : 0;
+}
+
+// what the two entry points share, every check before the first device call; size: bytes per element
+static int ilv_buffers(int64_t E, int64_t batch, const void* e, int64_t ld_e, const void* f, int64_t ld_f, int size) {
+    if (batch < 0) return fail(PL_EINVAL, "batch must be >= 0");
+    if (batch > 0 && (!e || !f)) return fail(PL_EINVAL, "device pointers must not be NULL");
+    if (((uintptr_t)e | (uintptr_t)f) & (uintptr_t)(size - 1))
+        return fail(PL_EINVAL, "e_dev and f_dev must be aligned to their element type");
+    if (ld_e < E) return fail(PL_EINVAL, "ld_e < E = " + std::to_string(E));
+    if (ld_f < E) return fail(PL_EINVAL, "ld_f < E = " + std::to_string(E));
+    if (batch > 0) {
+        // the bytes each side spans, rows and the gaps between them: [e, e + ne) against [f, f + nf)
+        const unsigned __int128 ne = ((unsigned __int128)(batch - 1) * ld_e + E) * size;
+        const unsigned __int128 nf = ((unsigned __int128)(batch - 1) * ld_f + E) * size;
+        const unsigned __int128 e0 = (uintptr_t)e, f0 = (uintptr_t)f;
+        if (e0 < f0 + nf && f0 < e0 + ne) return fail(PL_EINVAL, "e_dev and f_dev overlap");
+    }
+    return PL_OK;
+}
+
+extern "C" int pl_bit_interleave(int32_t kind, int32_t rows, int64_t E, int64_t batch, const uint8_t* e, int64_t ld_e,
+                                 uint8_t* f, int64_t ld_f, void* stream) {
+    pl::IlvParams p;
+    if (int rc = ilv_args(kind, rows, E, &p)) return rc;
+    if (int rc = ilv_buffers(E, batch, e, ld_e, f, ld_f, 1)) return rc;
+    const hipError_t err = pl::bit_interleave_launch(kind, p, e, ld_e, batch, f, ld_f, (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "bit interleave launch");
+}
+
+extern "C" int pl_llr_deinterleave(int32_t kind, int32_t rows, int64_t E, int64_t batch, const void* f, int64_t ld_f,
+                                   void* e, int64_t ld_e, int32_t flags, void* stream) {
+    pl::IlvParams p;
+    if (int rc = ilv_args(kind, rows, E, &p)) return rc;
+    if (flags & ~PL_ILV_LLR_F32) return fail(PL_EINVAL, "unknown flag bits");
+    const bool f32 = flags & PL_ILV_LLR_F32;
+    if (int rc = ilv_buffers(E, batch, e, ld_e, f, ld_f, f32 ? 4 : 8)) return rc;
+    const hipError_t err = pl::llr_deinterleave_launch(kind, p, f, ld_f, batch, e, ld_e, f32, (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "llr deinterleave launch");
+}
+
 extern "C" int pl_count_errors(const uint8_t* ref, int64_t ldr, const uint8_t* dec, int64_t ldd, int32_t width,
                                int64_t batch, int64_t* counts, void* stream) {
     if (batch < 0 || width < 0 || !counts || (batch > 0 && (!ref || !dec))) return fail(PL_EINVAL, "bad argument");

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "interleave_check.hpp"
 #include "ldpc_plan.hpp"
 
 #ifndef PL_METRIC_FUSED_NMAX
@@ -189,5 +190,15 @@ hipError_t qam_awgn_launch(int m, int64_t E, int64_t S, double scale, const uint
                            double sigma, uint64_t seed, int64_t off, double* y, int64_t ldy, hipStream_t s);
 hipError_t qam_demap_launch(int m, int64_t E, int64_t S, double scale, const double* y, int64_t ldy, int64_t batch,
                             double w, void* llr, int64_t ldl, bool llr_f32, hipStream_t s);
+
+// ---- the bit interleaver (interleave.hip); the definition: include/polarldpc.h, pl_interleave_check ----
+// kind, p checked (ilv_check).  e, f [batch][ld], pitches in elements: uint8 for the bits, double or float
+// (f32) for the LLRs.  Frames of at most kIlvLdsBytes are permuted in LDS, longer ones directly in global
+// memory.  Both chunk their launches themselves.
+constexpr int64_t kIlvLdsBytes = 65536;
+hipError_t bit_interleave_launch(int kind, const IlvParams& p, const uint8_t* e, int64_t lde, int64_t batch, uint8_t* f,
+                                 int64_t ldf, hipStream_t s);
+hipError_t llr_deinterleave_launch(int kind, const IlvParams& p, const void* f, int64_t ldf, int64_t batch, void* e,
+                                   int64_t lde, bool f32, hipStream_t s);
 
 }  // namespace pl

@@ -48,9 +48,24 @@ def _log(log_path, mc, **key):
     return PointLog(log_path, dict(key, round_frames=mc.batch * mc.world, lib=_native.build_id()))
 
 
+def _interleaver(interleaver, E, modulation):
+    """simulate_*'s interleaver argument as a channel.BitInterleaver of the transmitted length E: one is
+    checked against E; a (kind, rows) pair is built at E, rows None standing for the modem's bits per symbol
+    (kind "rect") or for no rows (kind "tri")."""
+    from ..channel.interleave import BitInterleaver
+    if not isinstance(interleaver, BitInterleaver):
+        kind, rows = interleaver
+        if kind == "rect" and rows is None:
+            assert modulation is not None, "a 'rect' interleaver needs its rows, or a modulation to take them from"
+            rows = modulation.m
+        interleaver = BitInterleaver(kind, E, rows=rows)
+    assert interleaver.E == E, "the interleaver's E = %d must be the transmitted length %d" % (interleaver.E, E)
+    return interleaver
+
+
 def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: int, config: Dict,
                    list_size: int = 0, crc_polynomial: Optional[str] = None, batch: int = 65536, seed: int = 0,
-                   group=None, log_path=None, rate_match=None, modulation=None):
+                   group=None, log_path=None, rate_match=None, modulation=None, interleaver=None):
     """ber_simulation.py:132-198 -> (ber, fer, points).  list_size 0 = SC (the
     reference), >= 1 = SCL, with crc_polynomial = CA-SCL (CRC inside the K bits).
     log_path: JSON-lines file of finished points; a rerun resumes from it.
@@ -65,7 +80,12 @@ def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: i
 
     modulation: None (BPSK), or a channel.QAMModem: the transmitted bits cross the
     channel as Gray-mapped QAM symbols (polar_round_fn's modulation) and snr_db is
-    Es/N0 per QAM symbol; its bits per symbol enter the run key only when given."""
+    Es/N0 per QAM symbol; its bits per symbol enter the run key only when given.
+
+    interleaver: None, a channel.BitInterleaver of the transmitted length (E, or N
+    without rate matching) or a (kind, rows) pair to build one there (rows None:
+    the modem's bits per symbol): polar_round_fn's interleaver.  [kind, rows]
+    enters the run key, as "interleave", only when given."""
     import torch
     from ..lib_wrappers import PolarLibWrapper
     from ..polar.decoder import CASCLDecoder, SCDecoder, SCLDecoder
@@ -83,6 +103,9 @@ def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: i
     if modulation is not None:
         more = dict(more, modulation=modulation.m)
         kw["modulation"] = modulation
+    if interleaver is not None:
+        kw["interleaver"] = _interleaver(interleaver, rm.E if rm is not None else N, modulation)
+        more = dict(more, interleave=kw["interleaver"].key)
     if list_size <= 0:
         dec = SCDecoder(N, K, frozen_bits=fr)
     elif crc_polynomial:
@@ -124,7 +147,7 @@ def simulate_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: in
 def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: int, base, Z: int,
                      max_iter: int = 20, normalization: float = 0.75, dtype=np.float64, batch: int = 65536,
                      seed: int = 0, group=None, random_codewords: bool = False, log_path=None, rate_match=None,
-                     fixed=None, modulation=None):
+                     fixed=None, modulation=None, interleaver=None):
     """simulate_ldpc for the quasi-cyclic code (base, Z): QCLayeredMSDecoder (layered
     normalised min-sum, early stop, state in `dtype`) on frames of the all-zero
     codeword or, random_codewords, of random messages encoded on the device from
@@ -144,7 +167,10 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
 
     modulation: None (BPSK), or a channel.QAMModem (ldpc_round_fn's modulation; it needs
     random_codewords); snr_db is then Es/N0 per QAM symbol, and its bits per symbol enter the
-    run key."""
+    run key.
+
+    interleaver: as simulate_polar's (the transmitted length is the matcher's E, or n);
+    ldpc_round_fn's interleaver, which needs random_codewords."""
     import torch
     from ..ldpc.decoder import QCFixedMSDecoder, QCLayeredMSDecoder
     from ..ldpc.encoder import QCLDPCEncoder
@@ -157,6 +183,11 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
     if modulation is not None:
         more["modulation"] = modulation.m
         kw["modulation"] = modulation
+
+    def with_interleaver(E):
+        if interleaver is not None:
+            kw["interleaver"] = _interleaver(interleaver, E, modulation)
+            more["interleave"] = kw["interleaver"].key
 
     def make_decoder(b):
         if fixed is None:
@@ -171,6 +202,7 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
         rm = QCRateMatcher(base, Z, **rate_match) if isinstance(rate_match, dict) else QCRateMatcher(base, Z, *rate_match)
         dec = make_decoder(rm.decoder_base())
         k = rm.k - rm.fillers
+        with_interleaver(rm.E)
         enc = QCLDPCEncoder(base, Z) if random_codewords else None
         mc = MonteCarlo(ldpc_round_fn(dec, seed=seed, encoder=enc, rate_matcher=rm, **kw), info_bits=k, batch=batch,
                         group=group, device=torch.device("cuda", torch.cuda.current_device()))
@@ -182,6 +214,7 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
         return np.array([p.ber for p in pts]), np.array([p.fer for p in pts]), pts
     dec = make_decoder(base)
     k = dec.n - dec.m
+    with_interleaver(dec.n)
     enc = QCLDPCEncoder(base, Z) if random_codewords else None
     mc = MonteCarlo(ldpc_round_fn(dec, seed=seed, info_bits=k, encoder=enc, **kw), info_bits=k, batch=batch, group=group,
                     device=torch.device("cuda", torch.cuda.current_device()))
@@ -263,6 +296,11 @@ def main(argv=None):
     ap.add_argument("--modulation", choices=["qpsk", "16qam", "64qam", "256qam"], default=None,
                     help="--code polar, qcldpc: Gray-mapped QAM (channel.QAMModem) instead of BPSK; --snr is then Es/N0 "
                          "per QAM symbol; qcldpc needs --ldpc-codewords random")
+    ap.add_argument("--interleave", choices=["rect", "tri"], default=None,
+                    help="--code polar, qcldpc: a bit interleaver (channel.BitInterleaver) between rate matching and "
+                         "the channel: row-column or triangular; qcldpc needs --ldpc-codewords random")
+    ap.add_argument("--interleave-rows", type=int, default=None,
+                    help="--interleave rect: its rows; default: the bits per symbol of --modulation")
     ap.add_argument("--norm", type=float, default=0.75, help="--code qcldpc: min-sum normalisation")
     ap.add_argument("--seed", type=int, default=0, help="--code qcldpc: seed of the frame source")
     ap.add_argument("--cpu-stub", action="store_true",
@@ -285,6 +323,14 @@ def main(argv=None):
             ap.error("--modulation goes with --code polar or qcldpc")
         from ..channel.qam import NAMES, QAMModem
         mod["modulation"] = QAMModem(NAMES[a.modulation])
+    if a.interleave is not None and not a.cpu_stub:
+        if a.code == "ldpc":
+            ap.error("--interleave goes with --code polar or qcldpc")
+        if a.interleave == "rect" and a.interleave_rows is None and a.modulation is None:
+            ap.error("--interleave rect needs --interleave-rows or --modulation")
+        if a.interleave == "tri" and a.interleave_rows is not None:
+            ap.error("--interleave-rows goes with --interleave rect")
+        mod["interleaver"] = (a.interleave, a.interleave_rows)
     if a.cpu_stub:
         from .montecarlo import stub_round_fn
         mc = MonteCarlo(stub_round_fn(seed=7, info_bits=a.K), info_bits=a.K, batch=a.batch)

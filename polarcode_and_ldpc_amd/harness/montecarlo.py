@@ -236,14 +236,39 @@ def _qam_channel(modem, bits, E, nframes, snr_db, seed, offset, bufs, rx):
     modem.demap(sym, E, snr_db, out=rx)
 
 
-def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm, modem=None):
+def _channel(modem, ilv, bits, E, nframes, snr_db, seed, offset, bufs, rx):
+    """The chains' channel for the E transmitted bits of each frame, into rx [nframes, E]: BPSK
+    (AWGNChannel.llr_batch_device) or, with a channel.QAMModem, _qam_channel.  With a channel.BitInterleaver
+    the bits are interleaved in front of it and the LLRs deinterleaved behind it, in rx's dtype; the
+    interleaved bits and LLRs live in bufs["ilv_tx"] and bufs["ilv_rx"]."""
+    if ilv is not None:
+        import torch
+        if "ilv_tx" not in bufs or bufs["ilv_tx"].shape[0] < nframes:
+            bufs["ilv_tx"] = torch.empty((nframes, E), dtype=torch.uint8, device="cuda")
+            bufs["ilv_rx"] = torch.empty((nframes, E), dtype=rx.dtype, device="cuda")
+        out, rx = rx, bufs["ilv_rx"][:nframes]
+        bits = ilv.interleave(bits, out=bufs["ilv_tx"][:nframes])
+    if modem is None:
+        from ..channel.awgn import AWGNChannel
+        AWGNChannel(snr_db).llr_batch_device(bits, E, nframes, seed=seed, frame_offset=offset, out=rx)
+    else:
+        _qam_channel(modem, bits, E, nframes, snr_db, seed, offset, bufs, rx)
+    if ilv is not None:
+        ilv.deinterleave(rx, out=out)
+
+
+def _check_interleaver(ilv, E):
+    assert ilv is None or ilv.E == E, "the interleaver's E = %d must be the transmitted length %d" % (ilv.E, E)
+
+
+def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm, modem=None, ilv=None):
     """polar_round_fn's rate-matched chain; see there."""
     import torch
     from .. import _native
-    from ..channel.awgn import AWGNChannel
     N, K, E = decoder.N, decoder._n_info, rm.E
     assert decoder.N == rm.N, "the decoder and the rate matcher must share the mother code: N = %d" % rm.N
     rm.check_frozen(decoder.frozen_bits)
+    _check_interleaver(ilv, E)
     bufs = {}
 
     def fn(snr_index, snr_db, offset, nframes):
@@ -259,10 +284,7 @@ def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm, modem=None):
         _polar_messages(msg, s, offset, K, crc_polynomial)
         _native.polar_encode(decoder.plan, msg, cw)
         rm.select(cw, out=tx)
-        if modem is None:
-            AWGNChannel(snr_db).llr_batch_device(tx, E, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=rx)
-        else:
-            _qam_channel(modem, tx, E, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, rx)
+        _channel(modem, ilv, tx, E, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, rx)
         rm.recover(rx, out=llr)
         decoder.plan.decode(llr, out)
         counts = torch.zeros(3, dtype=torch.int64, device="cuda")
@@ -272,7 +294,8 @@ def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm, modem=None):
     return fn
 
 
-def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None, rate_matcher=None, modulation=None):
+def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None, rate_matcher=None, modulation=None,
+                   interleaver=None):
     """Round function for a drop-in SC/SCL decoder (polar.SCDecoder/SCLDecoder).
     Random K-bit messages (CRC appended when crc_polynomial is given, as
     src/polar/encoder.py:74-78 does), device polar encoder, device AWGN,
@@ -289,13 +312,18 @@ def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None,
     modulation = a channel.QAMModem: the transmitted bits (the matcher's E, or the
     whole codeword) cross the channel as Gray-mapped QAM symbols, modem.awgn then
     modem.demap (max-log, fp64), with the seed derivation of the BPSK call; snr_db
-    is then Es/N0 per QAM symbol.  None: BPSK, every call as before."""
+    is then Es/N0 per QAM symbol.  None: BPSK, every call as before.
+
+    interleaver = a channel.BitInterleaver whose E is the transmitted length (the
+    matcher's E, or N): the chain becomes select, interleave, channel (BPSK or
+    QAM), deinterleave, recover (include/polarldpc.h at pl_interleave_check).
+    None: every call, seed and buffer as before."""
     if rate_matcher is not None:
-        return _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rate_matcher, modulation)
+        return _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rate_matcher, modulation, interleaver)
     import torch
     from .. import _native
-    from ..channel.awgn import AWGNChannel
     N, K = decoder.N, decoder._n_info
+    _check_interleaver(interleaver, N)
     bufs = {}
 
     def fn(snr_index, snr_db, offset, nframes):
@@ -315,10 +343,7 @@ def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None,
             _native.random_bits(s, offset, msg)
             _native.crc_append(msg, K - L, L, CRC_POLYNOMIALS[name])
         _native.polar_encode(decoder.plan, msg, cw)
-        if modulation is None:
-            AWGNChannel(snr_db).llr_batch_device(cw, N, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=llr)
-        else:
-            _qam_channel(modulation, cw, N, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, llr)
+        _channel(modulation, interleaver, cw, N, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, llr)
         decoder.plan.decode(llr, out)
         counts = torch.zeros(3, dtype=torch.int64, device="cuda")
         _native.count_errors(msg, out, K, counts)
@@ -335,7 +360,7 @@ def _plan_decode(decoder, llr, out, its):
     decoder.plan.decode(llr, out, its)
 
 
-def _rate_matched_round_fn(decoder, seed, encoder, rm, modem=None):
+def _rate_matched_round_fn(decoder, seed, encoder, rm, modem=None, ilv=None):
     """ldpc_round_fn's rate-matched chain; see there."""
     import torch
     from .. import _native
@@ -346,6 +371,7 @@ def _rate_matched_round_fn(decoder, seed, encoder, rm, modem=None):
     assert encoder is None or (encoder.n == rm.n and encoder.k == rm.k
                                and np.array_equal(encoder.info_positions, np.arange(rm.k))), \
         "the encoder must be the systematic encoder of the rate matcher's code"
+    _check_interleaver(ilv, E)
     ftype = torch.float32 if np.dtype(getattr(decoder, "dtype", np.float64)) == np.float32 else torch.float64
     bufs = {}
 
@@ -372,10 +398,7 @@ def _rate_matched_round_fn(decoder, seed, encoder, rm, modem=None):
             msg[:, kf:] = 0  # the fillers are known zeros
             encoder.encode_batch_device(msg, out=cw)
             rm.select(cw, out=tx)
-            if modem is None:
-                AWGNChannel(snr_db).llr_batch_device(tx, E, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=rx)
-            else:
-                _qam_channel(modem, tx, E, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, rx)
+            _channel(modem, ilv, tx, E, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, rx)
             ref = msg
         rm.recover(rx, out=llr)
         _plan_decode(decoder, llr, out, its)
@@ -386,7 +409,7 @@ def _rate_matched_round_fn(decoder, seed, encoder, rm, modem=None):
 
 
 def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encoder=None, rate_matcher=None,
-                  modulation=None):
+                  modulation=None, interleaver=None):
     """Round function for BPDecoder / MSDecoder / LayeredMSDecoder (any decoder
     with `.plan`, `.n` and `.m`).  A QCFixedMSDecoder takes the same chain: the
     channel LLRs (and the recovery) stay fp64 and the decoder quantises them.
@@ -410,16 +433,25 @@ def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encod
     details); the demapper writes fp32 for a float32 decoder, else fp64.  A QAM
     bit channel is not symmetric -- a bit's error probability depends on the
     other bits of its symbol -- so the all-zero codeword stands for nothing:
-    `encoder` is required.  None: BPSK, every call as before."""
+    `encoder` is required.  None: BPSK, every call as before.
+
+    interleaver = a channel.BitInterleaver whose E is the transmitted length (the
+    matcher's E, or n): select, interleave, channel, deinterleave (in the dtype
+    the channel wrote), recover.  The all-zero codeword shortcut transmits no
+    bits to interleave, so `encoder` is required here too.  None: every call as
+    before."""
     assert modulation is None or encoder is not None, \
         "modulation needs an encoder: the bit channels of a QAM symbol are not symmetric, so the all-zero " \
         "codeword shortcut is invalid"
+    assert interleaver is None or encoder is not None, \
+        "interleaver needs an encoder: the all-zero codeword shortcut transmits no bits to interleave"
     if rate_matcher is not None:
-        return _rate_matched_round_fn(decoder, seed, encoder, rate_matcher, modulation)
+        return _rate_matched_round_fn(decoder, seed, encoder, rate_matcher, modulation, interleaver)
     import torch
     from .. import _native
     from ..channel.awgn import AWGNChannel
     n = decoder.n
+    _check_interleaver(interleaver, n)
     if encoder is not None:
         k = encoder.k
         info = torch.from_numpy(np.asarray(encoder.info_positions, dtype=np.int64)).cuda()
@@ -447,10 +479,7 @@ def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encod
         else:
             _native.random_bits(s, offset, msg)
             encoder.encode_batch_device(msg, out=cw)
-            if modulation is None:
-                AWGNChannel(snr_db).llr_batch_device(cw, n, nframes, seed=s ^ 0xA5A5A5A5, frame_offset=offset, out=llr)
-            else:
-                _qam_channel(modulation, cw, n, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, llr)
+            _channel(modulation, interleaver, cw, n, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, llr)
             _plan_decode(decoder, llr, out, its)
             _native.count_errors(msg, out.index_select(1, info).contiguous(), k, counts)
         return counts.cpu().numpy()
