@@ -831,6 +831,68 @@ int pl_qam_awgn(int32_t m, int64_t E, int64_t batch, const uint8_t* e_dev, int64
 int pl_qam_demap(int32_t m, int64_t E, int64_t batch, const double* y_dev, int64_t ld_y, double snr_db, void* llr_dev,
                  int64_t ld_llr, int32_t flags, void* stream);
 
+/* ---- Block Rayleigh fading for the QAM symbols, and the demapper with channel state ----
+ * A channel whose gain is correlated over neighbouring symbols, which is what the bit
+ * interleaver is for, with perfect channel state at the receiver.  This comment is the
+ * definition; the kernels (qam.hip), channel.QAMModem and the harness cite it.  It builds on
+ * the block at pl_qam_check: its m, E, h bits per axis, S, scale, symbol layout, sigma and
+ * noise stream.
+ * Parameters and conditions; a violation is PL_EINVAL naming the first one violated, in
+ * this order:
+ *   1., 2. pl_qam_check's two, in its order
+ *   3. 1 <= coherence <= 2^30: the coherence length Lc, in symbols
+ * Derived: the fading block of symbol s is q = s / Lc (integer division); Q = ceil(S / Lc)
+ * blocks per frame.  Lc >= S: one coefficient per frame (quasi-static); Lc = 1: one per
+ * symbol (fast fading).
+ * Coefficients: fp64, real and imaginary part interleaved, [batch][ld_h], ld_h >= 2 Q:
+ *   element 2 q is Re and element 2 q + 1 is Im of block q.  hr = g0 * C, hi = g1 * C with
+ *   C = 0x1.6a09e667f3bcdp-1 (the double nearest 1 / sqrt(2)) and (g0, g1) the Box-Muller
+ *   pair of the stream contract at counter (q, f_lo, f_hi, 0xFADE9A3A), f = frame_offset + b,
+ *   key as the AWGN source.  A coefficient depends on (seed, f, q) only: not on Lc, m, E or
+ *   the batch.  E |h|^2 = 1.
+ * Channel: with the clean symbol (xI, xQ), each step one IEEE operation, in this order, no
+ *   contraction:
+ *     yI = (hr * xI - hi * xQ) + sigma * z0
+ *     yQ = (hr * xQ + hi * xI) + sigma * z1
+ *   (z0, z1) is exactly pl_qam_awgn's pair of symbol s (salt 0x9A3A9A3A): with equal seeds
+ *   the noise is pl_qam_awgn's noise.
+ * Demapper with channel state (max-log), exact fp64, every step one IEEE operation.  Per
+ *   symbol, with its block's (hr, hi):
+ *     g  = hr * hr + hi * hi
+ *     uI = hr * yI + hi * yQ          uQ = hr * yQ - hi * yI
+ *     rI = uI / g                     rQ = uQ / g
+ *     wg = w * g                      (w as pl_qam_demap: 1.0 / (2.0 * (sigma * sigma)), on the host)
+ *   and the LLR of axis bit p is (d1 - d0) * wg with d_a = (r - x_a) * (r - x_a) and the
+ *   minima as in pl_qam_demap.  The matched filter u = conj(h) y leaves r = y / h with noise
+ *   of variance sigma^2 / g per axis: the thresholds stay where they are and the weight
+ *   scales by g.  g == 0.0 (a zero or underflowing coefficient; u1 = 1 makes the Box-Muller
+ *   radius exactly 0, so the channel can produce it): every LLR of the symbol is +0.0, an
+ *   erased symbol.  Every other special (NaN, inf, a g so small that u / g overflows) gives
+ *   what the operations give; a NaN's payload is unspecified.  PL_QAM_LLR_F32: the fp64
+ *   result rounded once to fp32.
+ *   Property: with h = (1.0, 0.0) and finite y the result equals pl_qam_demap's bit for bit
+ *   (g = 1, u = y up to the sign of a zero, r = u, wg = w).
+ * pl_qam_fading_check makes no device call; S_out and Q_out may be NULL. */
+int pl_qam_fading_check(int32_t m, int64_t E, int64_t coherence, int64_t* S_out, int64_t* Q_out);
+/* y = h x + sigma z as defined above, mapped, faded and disturbed in one pass: y_dev double
+ * [batch][ld_y], ld_y >= 2 S; h_dev double [batch][ld_h], ld_h >= 2 Q, receives the
+ * coefficients; elements beyond 2 S and 2 Q of a row are left alone; y_dev and h_dev must not
+ * overlap.  e_dev == NULL: all-zero bits (ld_e is then not used).  Asynchronous on `stream`;
+ * batch == 0 launches nothing.  PL_EINVAL as pl_qam_awgn, and for what pl_qam_fading_check
+ * refuses, h_dev NULL with batch > 0, h_dev not 8-byte aligned and ld_h < 2 Q; every check
+ * runs before the first device call. */
+int pl_qam_rayleigh(int32_t m, int64_t E, int64_t coherence, int64_t batch, const uint8_t* e_dev, int64_t ld_e,
+                    double snr_db, uint64_t seed, int64_t frame_offset, double* y_dev, int64_t ld_y,
+                    double* h_dev, int64_t ld_h, void* stream);
+/* llr[b][t], t < E, of the received y_dev and the coefficients h_dev (layouts as above):
+ * llr_dev [batch][ld_llr], ld_llr >= E, float with PL_QAM_LLR_F32, else double; elements
+ * beyond E are left alone.  PL_EINVAL as pl_qam_demap and as pl_qam_rayleigh for coherence
+ * and h_dev.  The kernel stores whole 16-byte pieces as pl_qam_demap's does, whatever the
+ * pointer and the pitch. */
+int pl_qam_demap_csi(int32_t m, int64_t E, int64_t coherence, int64_t batch, const double* y_dev, int64_t ld_y,
+                     const double* h_dev, int64_t ld_h, double snr_db, void* llr_dev, int64_t ld_llr,
+                     int32_t flags, void* stream);
+
 /* ---- Bit interleaver between rate matching and the QAM modem ---------------------------
  * The m bit positions of a QAM symbol are unequally reliable and a rate matcher hands over
  * runs of consecutive code bits; the interleaver spreads such a run over the positions.

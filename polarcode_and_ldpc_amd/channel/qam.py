@@ -8,6 +8,10 @@ operation order -- is stated once, in include/polarldpc.h at pl_qam_check.
 modulate_host / demap_host are that definition in vectorised NumPy, bit for bit
 what the device kernels (csrc/qam.hip) compute; the device methods take NumPy in
 and give NumPy back, or CUDA tensors in and out with no host copy.
+
+Block Rayleigh fading of the symbols with channel state at the demapper (the
+definition: include/polarldpc.h at pl_qam_fading_check) rides on it: rayleigh /
+demap_csi on the device, fade_host / demap_csi_host as the definition in NumPy.
 """
 from __future__ import annotations
 
@@ -146,6 +150,114 @@ class QAMModem:
         assert llr.dtype in (torch.float32, torch.float64), "out must be float64 or float32"
         if r.shape[0]:
             _native.qam_demap(self.m, E, r, snr_db, llr, stream=stream)
+        return llr.cpu().numpy() if host and out is None else llr
+
+    # ---- block Rayleigh fading; the definition: include/polarldpc.h at pl_qam_fading_check ----
+    def blocks(self, E: int, coherence: int) -> int:
+        """Q, fading blocks per frame of E transmitted bits at a coherence length of `coherence` symbols"""
+        return _native.qam_fading_check(self.m, E, coherence)[1]
+
+    @staticmethod
+    def _per_symbol(h2, S, coherence):
+        """(hr, hi) [B, S] of the coefficients h2 [B, >= 2 Q]: symbol s takes block s // coherence"""
+        q = np.arange(S) // int(coherence)
+        assert h2.shape[1] >= 2 * (int(q[-1]) + 1), "h must hold 2 Q = %d values a frame" % (2 * (int(q[-1]) + 1))
+        return h2[:, 2 * q], h2[:, 2 * q + 1]
+
+    def fade_host(self, x, h, noise, coherence: int) -> np.ndarray:
+        """y = h x + noise by the definition's operations: x, noise float64 [B, 2 S] (or [2 S]; noise is sigma z),
+        h float64 [B, >= 2 Q] (or [>= 2 Q]), Re and Im interleaved -> float64 [B, 2 S] (or [2 S])."""
+        x = np.asarray(x, dtype=np.float64)
+        x2, n2 = np.atleast_2d(x), np.atleast_2d(np.asarray(noise, dtype=np.float64))
+        hr, hi = self._per_symbol(np.atleast_2d(np.asarray(h, dtype=np.float64)), x2.shape[1] // 2, coherence)
+        xi, xq = x2[:, 0::2], x2[:, 1::2]
+        y = np.empty_like(x2)
+        with np.errstate(over="ignore", invalid="ignore"):
+            y[:, 0::2] = (hr * xi - hi * xq) + n2[:, 0::2]
+            y[:, 1::2] = (hr * xq + hi * xi) + n2[:, 1::2]
+        return y[0] if x.ndim == 1 else y
+
+    def demap_csi_host(self, y, h, E: int, snr_db: float, coherence: int = 1, dtype=np.float64) -> np.ndarray:
+        """y float64 [B, >= 2 S], h float64 [B, >= 2 Q] (or one frame of each) -> LLRs [B, E] (or [E]) of `dtype`
+        (float64 or float32); a symbol whose |h|^2 is 0.0 gives +0.0."""
+        y = np.asarray(y, dtype=np.float64)
+        y2 = np.atleast_2d(y)
+        S = _native.qam_fading_check(self.m, E, coherence)[0]
+        assert y2.shape[1] >= 2 * S, "y must hold 2 S = %d values a frame" % (2 * S)
+        hr, hi = self._per_symbol(np.atleast_2d(np.asarray(h, dtype=np.float64)), S, coherence)
+        sigma = sigma_of(snr_db)
+        s2 = sigma * sigma
+        w = np.float64(1.0 / (2.0 * s2))
+        yi, yq = y2[:, 0:2 * S:2], y2[:, 1:2 * S:2]
+        with np.errstate(over="ignore", under="ignore", invalid="ignore", divide="ignore"):
+            g = hr * hr + hi * hi
+            ui = hr * yi + hi * yq
+            uq = hr * yq - hi * yi
+            r = np.stack([ui / g, uq / g], axis=-1)  # [B, S, axis]
+            wg = (w * g)[..., None]
+            t = r[..., None] - self.level_values
+            d = t * t  # [B, S, axis, level]
+            out = np.empty((r.shape[0], S, self.h, 2), dtype=np.float64)
+            for p in range(self.h):
+                one = self.level_bits[:, p] == 1
+                out[:, :, p, :] = (d[..., one].min(axis=-1) - d[..., ~one].min(axis=-1)) * wg
+            out[g == 0.0] = 0.0
+            llr = out.reshape(-1, S * self.m)[:, :E].astype(np.dtype(dtype))
+        return llr[0] if y.ndim == 1 else llr
+
+    def rayleigh(self, bits, E: int, batch: int, snr_db: float, seed: int, coherence: int = 1, frame_offset: int = 0,
+                 out=None, h_out=None, stream=None):
+        """Received symbols y = h x + sigma z and the coefficients h on the device (pl_qam_rayleigh), mapped, faded
+        and disturbed in one pass: bits as awgn's (uint8 [batch, E], CUDA tensor or NumPy, or None) -> (y float64
+        [batch, 2 S], h float64 [batch, 2 Q]), `out` and `h_out` if given (any row pitch; elements beyond stay
+        untouched).  Block q of frame b draws the stream (seed, frame_offset + b, q) whatever the coherence
+        length; the noise is awgn's for the same seed.  NumPy bits come back as NumPy."""
+        import torch
+        _native.require_gpu()
+        host = bits is not None and not isinstance(bits, torch.Tensor)
+        e = torch.from_numpy(np.array(bits, dtype=np.uint8)).cuda() if host else bits
+        E, batch = int(E), int(batch)
+        S, Q = _native.qam_fading_check(self.m, E, coherence)
+        if e is not None:
+            assert e.is_cuda and e.dtype == torch.uint8 and e.shape == (batch, E), "bits must be uint8 [batch, E]"
+            if e.stride(1) != 1 or (batch > 1 and e.stride(0) < E):
+                e = e.contiguous()
+        y = out if out is not None else torch.empty((batch, 2 * S), dtype=torch.float64, device="cuda")
+        h = h_out if h_out is not None else torch.empty((batch, 2 * Q), dtype=torch.float64, device="cuda")
+        self._check_out(y, batch, 2 * S, torch.float64, "out", "2 S")
+        self._check_out(h, batch, 2 * Q, torch.float64, "h_out", "2 Q")
+        if batch:
+            _native.qam_rayleigh(self.m, E, coherence, e, snr_db, seed, frame_offset, y, h, stream=stream)
+        if host:
+            return (y.cpu().numpy() if out is None else y), (h.cpu().numpy() if h_out is None else h)
+        return y, h
+
+    def demap_csi(self, y, h, E: int, snr_db: float, coherence: int = 1, dtype=np.float64, out=None, stream=None):
+        """Max-log LLRs with channel state on the device (pl_qam_demap_csi): y float64 [B, >= 2 S] and h float64
+        [B, >= 2 Q], CUDA tensors (unit inner stride, any row pitch) -> [B, E] CUDA tensor of `dtype` (float64 or
+        float32), `out` if given (its dtype counts; any row pitch >= E; elements beyond E stay untouched).  NumPy
+        arrays go to the device and the result comes back as NumPy."""
+        import torch
+        host = not isinstance(y, torch.Tensor)
+        r = torch.from_numpy(np.array(y, dtype=np.float64)).cuda() if host else y
+        c = torch.from_numpy(np.array(h, dtype=np.float64)).cuda() if not isinstance(h, torch.Tensor) else h
+        E = int(E)
+        S, Q = _native.qam_fading_check(self.m, E, coherence)
+        assert r.is_cuda and r.dtype == torch.float64 and r.dim() == 2 and r.shape[1] >= 2 * S, \
+            "y must be float64 [B, >= 2 S = %d]" % (2 * S)
+        assert c.is_cuda and c.dtype == torch.float64 and c.dim() == 2 and c.shape[0] == r.shape[0] \
+            and c.shape[1] >= 2 * Q, "h must be float64 [B, >= 2 Q = %d]" % (2 * Q)
+        if r.stride(1) != 1 or (r.shape[0] > 1 and r.stride(0) < 2 * S):
+            r = r.contiguous()
+        if c.stride(1) != 1 or (c.shape[0] > 1 and c.stride(0) < 2 * Q):
+            c = c.contiguous()
+        tdt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
+        assert tdt == torch.float32 or np.dtype(dtype) == np.float64, "dtype must be float64 or float32"
+        llr = out if out is not None else torch.empty((r.shape[0], E), dtype=tdt, device="cuda")
+        self._check_out(llr, r.shape[0], E, llr.dtype if out is not None else tdt, "out", "E")
+        assert llr.dtype in (torch.float32, torch.float64), "out must be float64 or float32"
+        if r.shape[0]:
+            _native.qam_demap_csi(self.m, E, coherence, r, c, snr_db, llr, stream=stream)
         return llr.cpu().numpy() if host and out is None else llr
 
     @staticmethod

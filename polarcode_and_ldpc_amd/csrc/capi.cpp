@@ -1473,6 +1473,60 @@ extern "C" int pl_qam_demap(int32_t m, int64_t E, int64_t batch, const double* y
     return err == hipSuccess ? PL_OK : hipfail(err, "qam demap launch");
 }
 
+// ---- block Rayleigh fading for the QAM symbols (qam.hip); the definition: include/polarldpc.h, pl_qam_fading_check ----
+extern "C" int pl_qam_fading_check(int32_t m, int64_t E, int64_t coherence, int64_t* S, int64_t* Q) {
+    const pl::QamStatus st = pl::qam_fading_check(m, E, coherence, S, Q);
+    return st.code ? fail(st.code, st.msg) : PL_OK;
+}
+
+// what the two entry points share behind the parameters, every check before the first device call
+static int qam_fading_buffers(int64_t batch, const double* y, int64_t ld_y, const double* h, int64_t ld_h, int64_t S,
+                              int64_t Q) {
+    if (batch < 0) return fail(PL_EINVAL, "batch must be >= 0");
+    if (batch > 0 && !y) return fail(PL_EINVAL, "y_dev must not be NULL");
+    if (batch > 0 && !h) return fail(PL_EINVAL, "h_dev must not be NULL");
+    if (((uintptr_t)y | (uintptr_t)h) & 7) return fail(PL_EINVAL, "y_dev and h_dev must be aligned to their element type");
+    if (ld_y < 2 * S) return fail(PL_EINVAL, "ld_y < 2 S = " + std::to_string(2 * S));
+    if (ld_h < 2 * Q) return fail(PL_EINVAL, "ld_h < 2 Q = " + std::to_string(2 * Q));
+    return PL_OK;
+}
+
+extern "C" int pl_qam_rayleigh(int32_t m, int64_t E, int64_t coherence, int64_t batch, const uint8_t* e, int64_t ld_e,
+                               double snr_db, uint64_t seed, int64_t frame_offset, double* y, int64_t ld_y, double* h,
+                               int64_t ld_h, void* stream) {
+    int64_t S, Q;
+    double scale, sigma;
+    if (int rc = pl_qam_fading_check(m, E, coherence, &S, &Q)) return rc;
+    if (int rc = qam_fading_buffers(batch, y, ld_y, h, ld_h, S, Q)) return rc;
+    if (int rc = qam_sigma(snr_db, &sigma)) return rc;
+    if (e && ld_e < E) return fail(PL_EINVAL, "ld_e < E = " + std::to_string(E));
+    pl::qam_check(m, E, nullptr, &scale);
+    const hipError_t err = pl::qam_rayleigh_launch(m, E, S, coherence, scale, e, ld_e, batch, sigma, seed, frame_offset,
+                                                   y, ld_y, h, ld_h, (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "qam rayleigh launch");
+}
+
+extern "C" int pl_qam_demap_csi(int32_t m, int64_t E, int64_t coherence, int64_t batch, const double* y, int64_t ld_y,
+                                const double* h, int64_t ld_h, double snr_db, void* llr, int64_t ld_llr, int32_t flags,
+                                void* stream) {
+    int64_t S, Q;
+    double scale, sigma;
+    if (int rc = pl_qam_fading_check(m, E, coherence, &S, &Q)) return rc;
+    if (int rc = qam_fading_buffers(batch, y, ld_y, h, ld_h, S, Q)) return rc;
+    if (batch > 0 && !llr) return fail(PL_EINVAL, "llr_dev must not be NULL");
+    if (flags & ~PL_QAM_LLR_F32) return fail(PL_EINVAL, "unknown flag bits");
+    if (int rc = qam_sigma(snr_db, &sigma)) return rc;
+    if ((uintptr_t)llr & ((flags & PL_QAM_LLR_F32) ? 3 : 7))
+        return fail(PL_EINVAL, "llr_dev must be aligned to its element type");
+    if (ld_llr < E) return fail(PL_EINVAL, "ld_llr < E = " + std::to_string(E));
+    pl::qam_check(m, E, nullptr, &scale);
+    const double s2 = sigma * sigma;
+    const double w = 1.0 / (2.0 * s2);
+    const hipError_t err = pl::qam_demap_csi_launch(m, E, S, coherence, scale, y, ld_y, h, ld_h, batch, w, llr, ld_llr,
+                                                    flags & PL_QAM_LLR_F32, (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, "qam demap csi launch");
+}
+
 // ---- the bit interleaver (interleave.hip); the definition: include/polarldpc.h, pl_interleave_check ----
 static int ilv_args(int32_t kind, int32_t rows, int64_t E, pl::IlvParams* p) {
     const pl::IlvStatus st = pl::ilv_check(kind, rows, E, p);

@@ -190,6 +190,14 @@ hipError_t qam_awgn_launch(int m, int64_t E, int64_t S, double scale, const uint
                            double sigma, uint64_t seed, int64_t off, double* y, int64_t ldy, hipStream_t s);
 hipError_t qam_demap_launch(int m, int64_t E, int64_t S, double scale, const double* y, int64_t ldy, int64_t batch,
                             double w, void* llr, int64_t ldl, bool llr_f32, hipStream_t s);
+// Block Rayleigh fading (the definition: include/polarldpc.h, pl_qam_fading_check): m, E, Lc checked
+// (qam_fading_check), S from it; h double [batch][ldh] of 2 Q used elements, Re and Im interleaved.
+hipError_t qam_rayleigh_launch(int m, int64_t E, int64_t S, int64_t Lc, double scale, const uint8_t* e, int64_t lde,
+                               int64_t batch, double sigma, uint64_t seed, int64_t off, double* y, int64_t ldy,
+                               double* h, int64_t ldh, hipStream_t s);
+hipError_t qam_demap_csi_launch(int m, int64_t E, int64_t S, int64_t Lc, double scale, const double* y, int64_t ldy,
+                                const double* h, int64_t ldh, int64_t batch, double w, void* llr, int64_t ldl,
+                                bool llr_f32, hipStream_t s);
 
 // ---- the bit interleaver (interleave.hip); the definition: include/polarldpc.h, pl_interleave_check ----
 // kind, p checked (ilv_check).  e, f [batch][ld], pitches in elements: uint8 for the bits, double or float

@@ -13,9 +13,16 @@
 //     computed once and each of the H bits takes its two minima over them (the level sets are compile-time
 //     masks).  A whole group goes out as `head` single elements, 16-byte stores, and the rest as single
 //     elements; the group cut by the row's end goes out element by element.
+// Block Rayleigh fading (the definition: include/polarldpc.h at pl_qam_fading_check) rides on both mappings:
+//   qam_rayleigh_kernel<H>: qam_tx_kernel's thread a symbol, with the coefficient of the symbol's fading block
+//     (a second Box-Muller pair, salt SALT_FADE, counter q = s / Lc) recomputed by every thread of the block
+//     and written by the block's first symbol.
+//   qam_demap_csi_kernel<H, T>: qam_demap_kernel's groups and stores; per symbol one more 16-byte load (the
+//     coefficient), five products, two divisions, and the erased symbol (|h|^2 == 0.0 -> +0.0).
 // Launches stay below 2^31 work-items (row chunks), so work-item indices are 32-bit.
 #include "common.hpp"
 #include "internal.hpp"
+#include "qam_check.hpp"
 
 namespace pl {
 
@@ -173,6 +180,145 @@ qam_demap_kernel(const double* __restrict__ y, int64_t ldy, uint32_t E, uint32_t
     }
 }
 
+// ---- block Rayleigh fading; the definition: include/polarldpc.h at pl_qam_fading_check ----
+// The pieces of the two kernels above that the fading kernels share with them, as functions (the kernels above keep
+// their own text: their code is not to change).
+// the clean symbol s of row `row`: its m codeword bytes (zeros behind E, and all zeros without e) -> (vi, vq)
+template <int H>
+PL_DEV void qam_symbol(const uint8_t* __restrict__ e, int64_t lde, uint32_t E, uint32_t row, uint32_t s, double scale,
+                       double& vi, double& vq) {
+    constexpr uint32_t M = 2 * H;
+    uint32_t bi[H] = {}, bq[H] = {};
+    if (e) {
+        const uint8_t* src = e + (int64_t)row * lde;
+        const uint32_t t0 = s * M;  // < E <= 2^30
+#pragma unroll
+        for (int p = 0; p < H; ++p) {
+            bi[p] = t0 + 2 * p < E ? src[t0 + 2 * p] & 1u : 0u;
+            bq[p] = t0 + 2 * p + 1 < E ? src[t0 + 2 * p + 1] & 1u : 0u;
+        }
+    }
+    vi = (double)qam_level<H>(bi) * scale;
+    vq = (double)qam_level<H>(bq) * scale;
+}
+
+// two doubles at o / from p, 16 bytes at once where the address allows
+PL_DEV void qam_store2(double* o, double a, double b) {
+    if (((uintptr_t)o & 15u) == 0) {
+        *reinterpret_cast<double2*>(o) = make_double2(a, b);
+    } else {
+        o[0] = a;
+        o[1] = b;
+    }
+}
+
+PL_DEV void qam_load2(const double* p, double& a, double& b) {
+    if (((uintptr_t)p & 15u) == 0) {
+        const double2 pr = *reinterpret_cast<const double2*>(p);
+        a = pr.x;
+        b = pr.y;
+    } else {
+        a = p[0];
+        b = p[1];
+    }
+}
+
+// a group of a row with `left` elements to the row's end: whole (left >= V) from the 16-byte boundary `head`
+// elements on, the one cut by the row's end element by element
+template <int V, typename T>
+PL_DEV void qam_store_cut(T* o, const T (&v)[V], uint32_t left) {
+    constexpr uint32_t EPT = 16 / sizeof(T);
+    if (left >= (uint32_t)V) {
+        const uint32_t head = ((uint32_t)(-(uintptr_t)o) & 15u) / (uint32_t)sizeof(T);
+        if (head == 0) {
+            qam_store_group<0, V, T>(o, v);
+        } else if constexpr (EPT == 2) {
+            qam_store_group<1, V, T>(o, v);
+        } else {
+            if (head == 1) qam_store_group<1, V, T>(o, v);
+            else if (head == 2) qam_store_group<2, V, T>(o, v);
+            else qam_store_group<3, V, T>(o, v);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+            if ((uint32_t)j < left) o[j] = v[j];
+    }
+}
+
+constexpr double kFadeC = 0x1.6a09e667f3bcdp-1;  // the double nearest 1 / sqrt(2)
+
+// the coefficient of fading block q of frame f: (seed, f, q) only
+PL_DEV void qam_fade_coeff(uint64_t seed, uint32_t q, uint64_t f, double& hr, double& hi) {
+    double g0, g1;
+    normal_pair(seed, SALT_FADE, q, f, g0, g1);
+    hr = g0 * kFadeC;
+    hi = g1 * kFadeC;
+}
+
+// qam_tx_kernel's mapping, one thread a symbol.  Every thread computes its block's coefficient itself (a wave runs
+// the Box-Muller path as soon as one lane needs it); the block's first symbol writes it.
+template <int H>
+__global__ void __launch_bounds__(kQamThreads)
+qam_rayleigh_kernel(const uint8_t* __restrict__ e, int64_t lde, uint32_t E, uint32_t S, uint32_t Lc, uint32_t total,
+                    double scale, double sigma, uint64_t seed, uint64_t f0, double* __restrict__ out, int64_t ldo,
+                    double* __restrict__ h, int64_t ldh) {
+    const uint32_t idx = blockIdx.x * kQamThreads + threadIdx.x;
+    if (idx >= total) return;
+    const uint32_t row = idx / S, s = idx - row * S, q = s / Lc;
+    double xi, xq, hr, hi, z0, z1;
+    qam_symbol<H>(e, lde, E, row, s, scale, xi, xq);
+    qam_fade_coeff(seed, q, f0 + row, hr, hi);
+    normal_pair(seed, kQamSalt, s, f0 + row, z0, z1);
+    const double yi = (hr * xi - hi * xq) + sigma * z0;
+    const double yq = (hr * xq + hi * xi) + sigma * z1;
+    qam_store2(out + (int64_t)row * ldo + 2 * (int64_t)s, yi, yq);
+    if (s == q * Lc) qam_store2(h + (int64_t)row * ldh + 2 * (int64_t)q, hr, hi);
+}
+
+// qam_demap_kernel with the channel state: per symbol the coefficient of its block, the matched filter u = conj(h) y,
+// r = u / |h|^2 and the weight w |h|^2; a symbol with |h|^2 == 0.0 is erased, every LLR +0.0.
+template <int H, typename T>
+__global__ void __launch_bounds__(kQamThreads)
+qam_demap_csi_kernel(const double* __restrict__ y, int64_t ldy, const double* __restrict__ h, int64_t ldh, uint32_t E,
+                     uint32_t S, uint32_t Lc, uint32_t W, uint32_t total, double scale, double w, T* __restrict__ llr,
+                     int64_t ldl) {
+    constexpr uint32_t M = 2 * H;
+    constexpr uint32_t G = (sizeof(T) == 4 && (H & 1)) ? 2 : 1;
+    constexpr uint32_t V = G * M;
+    static_assert(V % (16 / sizeof(T)) == 0, "a group is whole 16-byte pieces");
+    const uint32_t idx = blockIdx.x * kQamThreads + threadIdx.x;
+    if (idx >= total) return;
+    const uint32_t row = idx / W, g = idx - row * W;
+    const double* src = y + (int64_t)row * ldy;
+    const double* hsrc = h + (int64_t)row * ldh;
+    T v[V];
+#pragma unroll
+    for (uint32_t k = 0; k < G; ++k) {
+        const uint32_t s = g * G + k;
+        double yi = 0.0, yq = 0.0, hr = 1.0, hi = 0.0;  // a symbol behind S: its LLRs are not stored
+        if (s < S) {
+            qam_load2(src + 2 * (int64_t)s, yi, yq);
+            qam_load2(hsrc + 2 * (int64_t)(s / Lc), hr, hi);
+        }
+        const double g2 = hr * hr + hi * hi;
+        const double ui = hr * yi + hi * yq;
+        const double uq = hr * yq - hi * yi;
+        const double wg = w * g2;
+        double li[H], lq[H];
+        qam_axis_llr<H>(ui / g2, scale, wg, li);
+        qam_axis_llr<H>(uq / g2, scale, wg, lq);
+        const bool erased = g2 == 0.0;
+#pragma unroll
+        for (int p = 0; p < H; ++p) {
+            v[k * M + 2 * p] = erased ? (T)0.0 : (T)li[p];
+            v[k * M + 2 * p + 1] = erased ? (T)0.0 : (T)lq[p];
+        }
+    }
+    const uint32_t t0 = g * V;  // < E: W = ceil(E / V)
+    qam_store_cut<V, T>(llr + (int64_t)row * ldl + t0, v, E - t0);
+}
+
 // rows of W work-items each, in launches below 2^31 work-items; fn(first row, work-items)
 template <class Launch>
 static hipError_t qam_chunks(int64_t batch, int64_t W, Launch fn) {
@@ -248,6 +394,64 @@ hipError_t qam_demap_launch(int m, int64_t E, int64_t S, double scale, const dou
     if (batch == 0) return hipSuccess;
     return llr_f32 ? qam_demap_m(m, E, S, scale, y, ldy, batch, w, (float*)llr, ldl, s)
                    : qam_demap_m(m, E, S, scale, y, ldy, batch, w, (double*)llr, ldl, s);
+}
+
+template <int H>
+static hipError_t qam_rayleigh(const uint8_t* e, int64_t lde, int64_t E, int64_t S, int64_t Lc, int64_t batch,
+                               double scale, double sigma, uint64_t seed, int64_t off, double* y, int64_t ldy, double* h,
+                               int64_t ldh, hipStream_t st) {
+    return qam_chunks(batch, S, [&](int64_t b0, uint32_t total) {
+        hipLaunchKernelGGL((qam_rayleigh_kernel<H>), dim3((total + kQamThreads - 1) / kQamThreads), dim3(kQamThreads), 0,
+                           st, e ? e + b0 * lde : e, lde, (uint32_t)E, (uint32_t)S, (uint32_t)Lc, total, scale, sigma,
+                           seed, (uint64_t)(off + b0), y + b0 * ldy, ldy, h + b0 * ldh, ldh);
+        return hipGetLastError();
+    });
+}
+
+hipError_t qam_rayleigh_launch(int m, int64_t E, int64_t S, int64_t Lc, double scale, const uint8_t* e, int64_t lde,
+                               int64_t batch, double sigma, uint64_t seed, int64_t off, double* y, int64_t ldy,
+                               double* h, int64_t ldh, hipStream_t s) {
+    if (batch == 0) return hipSuccess;
+    switch (m) {
+        case 2: return qam_rayleigh<1>(e, lde, E, S, Lc, batch, scale, sigma, seed, off, y, ldy, h, ldh, s);
+        case 4: return qam_rayleigh<2>(e, lde, E, S, Lc, batch, scale, sigma, seed, off, y, ldy, h, ldh, s);
+        case 6: return qam_rayleigh<3>(e, lde, E, S, Lc, batch, scale, sigma, seed, off, y, ldy, h, ldh, s);
+        default: return qam_rayleigh<4>(e, lde, E, S, Lc, batch, scale, sigma, seed, off, y, ldy, h, ldh, s);
+    }
+}
+
+template <int H, typename T>
+static hipError_t qam_demap_csi(int64_t E, int64_t S, int64_t Lc, double scale, const double* y, int64_t ldy,
+                                const double* h, int64_t ldh, int64_t batch, double w, T* llr, int64_t ldl,
+                                hipStream_t st) {
+    constexpr int64_t V = ((sizeof(T) == 4 && (H & 1)) ? 2 : 1) * 2 * H;
+    const int64_t W = (E + V - 1) / V;
+    return qam_chunks(batch, W, [&](int64_t b0, uint32_t total) {
+        hipLaunchKernelGGL((qam_demap_csi_kernel<H, T>), dim3((total + kQamThreads - 1) / kQamThreads),
+                           dim3(kQamThreads), 0, st, y + b0 * ldy, ldy, h + b0 * ldh, ldh, (uint32_t)E, (uint32_t)S,
+                           (uint32_t)Lc, (uint32_t)W, total, scale, w, llr + b0 * ldl, ldl);
+        return hipGetLastError();
+    });
+}
+
+template <typename T>
+static hipError_t qam_demap_csi_m(int m, int64_t E, int64_t S, int64_t Lc, double scale, const double* y, int64_t ldy,
+                                  const double* h, int64_t ldh, int64_t batch, double w, T* llr, int64_t ldl,
+                                  hipStream_t st) {
+    switch (m) {
+        case 2: return qam_demap_csi<1, T>(E, S, Lc, scale, y, ldy, h, ldh, batch, w, llr, ldl, st);
+        case 4: return qam_demap_csi<2, T>(E, S, Lc, scale, y, ldy, h, ldh, batch, w, llr, ldl, st);
+        case 6: return qam_demap_csi<3, T>(E, S, Lc, scale, y, ldy, h, ldh, batch, w, llr, ldl, st);
+        default: return qam_demap_csi<4, T>(E, S, Lc, scale, y, ldy, h, ldh, batch, w, llr, ldl, st);
+    }
+}
+
+hipError_t qam_demap_csi_launch(int m, int64_t E, int64_t S, int64_t Lc, double scale, const double* y, int64_t ldy,
+                                const double* h, int64_t ldh, int64_t batch, double w, void* llr, int64_t ldl,
+                                bool llr_f32, hipStream_t s) {
+    if (batch == 0) return hipSuccess;
+    return llr_f32 ? qam_demap_csi_m(m, E, S, Lc, scale, y, ldy, h, ldh, batch, w, (float*)llr, ldl, s)
+                   : qam_demap_csi_m(m, E, S, Lc, scale, y, ldy, h, ldh, batch, w, (double*)llr, ldl, s);
 }
 
 }  // namespace pl

@@ -18,4 +18,15 @@ QamStatus qam_check(int32_t m, int64_t E, int64_t* S, double* scale) {
     return {};
 }
 
+QamStatus qam_fading_check(int32_t m, int64_t E, int64_t coherence, int64_t* S, int64_t* Q) {
+    int64_t s = 0;
+    QamStatus st = qam_check(m, E, &s, nullptr);
+    if (st.code) return st;
+    if (coherence < 1 || coherence > kQamMaxCoherence)
+        return {PL_EINVAL, "coherence = " + std::to_string(coherence) + " outside 1 .. 2^30"};
+    if (S) *S = s;
+    if (Q) *Q = (s + coherence - 1) / coherence;  // s <= 2^30 and coherence <= 2^30: no overflow
+    return {};
+}
+
 }  // namespace pl

@@ -65,7 +65,7 @@ def _interleaver(interleaver, E, modulation):
 
 def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: int, config: Dict,
                    list_size: int = 0, crc_polynomial: Optional[str] = None, batch: int = 65536, seed: int = 0,
-                   group=None, log_path=None, rate_match=None, modulation=None, interleaver=None):
+                   group=None, log_path=None, rate_match=None, modulation=None, interleaver=None, fading=None):
     """ber_simulation.py:132-198 -> (ber, fer, points).  list_size 0 = SC (the
     reference), >= 1 = SCL, with crc_polynomial = CA-SCL (CRC inside the K bits).
     log_path: JSON-lines file of finished points; a rerun resumes from it.
@@ -85,7 +85,11 @@ def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: i
     interleaver: None, a channel.BitInterleaver of the transmitted length (E, or N
     without rate matching) or a (kind, rows) pair to build one there (rows None:
     the modem's bits per symbol): polar_round_fn's interleaver.  [kind, rows]
-    enters the run key, as "interleave", only when given."""
+    enters the run key, as "interleave", only when given.
+
+    fading: None, or a coherence length in symbols: block Rayleigh fading of the QAM
+    symbols with channel state at the demapper (polar_round_fn's fading; it needs a
+    modulation).  It enters the run key, as "fading", only when given."""
     import torch
     from ..lib_wrappers import PolarLibWrapper
     from ..polar.decoder import CASCLDecoder, SCDecoder, SCLDecoder
@@ -106,6 +110,9 @@ def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: i
     if interleaver is not None:
         kw["interleaver"] = _interleaver(interleaver, rm.E if rm is not None else N, modulation)
         more = dict(more, interleave=kw["interleaver"].key)
+    if fading is not None:
+        kw["fading"] = int(fading)
+        more = dict(more, fading=int(fading))
     if list_size <= 0:
         dec = SCDecoder(N, K, frozen_bits=fr)
     elif crc_polynomial:
@@ -147,7 +154,7 @@ def simulate_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: in
 def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: int, base, Z: int,
                      max_iter: int = 20, normalization: float = 0.75, dtype=np.float64, batch: int = 65536,
                      seed: int = 0, group=None, random_codewords: bool = False, log_path=None, rate_match=None,
-                     fixed=None, modulation=None, interleaver=None):
+                     fixed=None, modulation=None, interleaver=None, fading=None):
     """simulate_ldpc for the quasi-cyclic code (base, Z): QCLayeredMSDecoder (layered
     normalised min-sum, early stop, state in `dtype`) on frames of the all-zero
     codeword or, random_codewords, of random messages encoded on the device from
@@ -170,7 +177,9 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
     run key.
 
     interleaver: as simulate_polar's (the transmitted length is the matcher's E, or n);
-    ldpc_round_fn's interleaver, which needs random_codewords."""
+    ldpc_round_fn's interleaver, which needs random_codewords.
+
+    fading: as simulate_polar's (ldpc_round_fn's fading)."""
     import torch
     from ..ldpc.decoder import QCFixedMSDecoder, QCLayeredMSDecoder
     from ..ldpc.encoder import QCLDPCEncoder
@@ -183,6 +192,8 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
     if modulation is not None:
         more["modulation"] = modulation.m
         kw["modulation"] = modulation
+    if fading is not None:
+        more["fading"] = kw["fading"] = int(fading)
 
     def with_interleaver(E):
         if interleaver is not None:
@@ -301,6 +312,9 @@ def main(argv=None):
                          "the channel: row-column or triangular; qcldpc needs --ldpc-codewords random")
     ap.add_argument("--interleave-rows", type=int, default=None,
                     help="--interleave rect: its rows; default: the bits per symbol of --modulation")
+    ap.add_argument("--fading", default=None, metavar="LC",
+                    help="with --modulation: block Rayleigh fading with channel state at the demapper; LC is the "
+                         "coherence length in symbols (1: fast fading), or 'frame' for one coefficient a frame")
     ap.add_argument("--norm", type=float, default=0.75, help="--code qcldpc: min-sum normalisation")
     ap.add_argument("--seed", type=int, default=0, help="--code qcldpc: seed of the frame source")
     ap.add_argument("--cpu-stub", action="store_true",
@@ -323,6 +337,13 @@ def main(argv=None):
             ap.error("--modulation goes with --code polar or qcldpc")
         from ..channel.qam import NAMES, QAMModem
         mod["modulation"] = QAMModem(NAMES[a.modulation])
+    if a.fading is not None:
+        if a.fading != "frame" and not a.fading.isdigit():
+            ap.error("--fading takes a coherence length in symbols, or 'frame'")
+        if a.modulation is None:
+            ap.error("--fading needs --modulation")
+        if not a.cpu_stub:
+            mod["fading"] = 1 << 30 if a.fading == "frame" else int(a.fading)
     if a.interleave is not None and not a.cpu_stub:
         if a.code == "ldpc":
             ap.error("--interleave goes with --code polar or qcldpc")

@@ -223,22 +223,31 @@ def _polar_messages(msg, s, offset, K, crc_polynomial):
         _native.crc_append(msg, K - L, L, CRC_POLYNOMIALS[name])
 
 
-def _qam_channel(modem, bits, E, nframes, snr_db, seed, offset, bufs, rx):
+def _qam_channel(modem, bits, E, nframes, snr_db, seed, offset, bufs, rx, fading=None):
     """The chains' channel with a channel.QAMModem: the E transmitted bits of each frame through modem.awgn
     (seed and frame offset as the BPSK call's) and modem.demap into rx [nframes, E], whose dtype the next
-    stage reads.  The symbols live in bufs["sym"]."""
+    stage reads.  The symbols live in bufs["sym"].  With fading, a coherence length in symbols, modem.rayleigh
+    and modem.demap_csi instead, same seed and offset; the coefficients live in bufs["csi"]."""
     import torch
     S2 = 2 * modem.S(E)
     if "sym" not in bufs or bufs["sym"].shape[0] < nframes:
         bufs["sym"] = torch.empty((nframes, S2), dtype=torch.float64, device="cuda")
     sym = bufs["sym"][:nframes]
-    modem.awgn(bits, E, nframes, snr_db, seed, frame_offset=offset, out=sym)
-    modem.demap(sym, E, snr_db, out=rx)
+    if fading is None:
+        modem.awgn(bits, E, nframes, snr_db, seed, frame_offset=offset, out=sym)
+        modem.demap(sym, E, snr_db, out=rx)
+        return
+    if "csi" not in bufs or bufs["csi"].shape[0] < nframes:
+        bufs["csi"] = torch.empty((nframes, 2 * modem.blocks(E, fading)), dtype=torch.float64, device="cuda")
+    csi = bufs["csi"][:nframes]
+    modem.rayleigh(bits, E, nframes, snr_db, seed, coherence=fading, frame_offset=offset, out=sym, h_out=csi)
+    modem.demap_csi(sym, csi, E, snr_db, coherence=fading, out=rx)
 
 
-def _channel(modem, ilv, bits, E, nframes, snr_db, seed, offset, bufs, rx):
+def _channel(modem, ilv, bits, E, nframes, snr_db, seed, offset, bufs, rx, fading=None):
     """The chains' channel for the E transmitted bits of each frame, into rx [nframes, E]: BPSK
-    (AWGNChannel.llr_batch_device) or, with a channel.QAMModem, _qam_channel.  With a channel.BitInterleaver
+    (AWGNChannel.llr_batch_device) or, with a channel.QAMModem, _qam_channel (fading: its block Rayleigh
+    fading, which _check_fading ties to a modem).  With a channel.BitInterleaver
     the bits are interleaved in front of it and the LLRs deinterleaved behind it, in rx's dtype; the
     interleaved bits and LLRs live in bufs["ilv_tx"] and bufs["ilv_rx"]."""
     if ilv is not None:
@@ -252,7 +261,7 @@ def _channel(modem, ilv, bits, E, nframes, snr_db, seed, offset, bufs, rx):
         from ..channel.awgn import AWGNChannel
         AWGNChannel(snr_db).llr_batch_device(bits, E, nframes, seed=seed, frame_offset=offset, out=rx)
     else:
-        _qam_channel(modem, bits, E, nframes, snr_db, seed, offset, bufs, rx)
+        _qam_channel(modem, bits, E, nframes, snr_db, seed, offset, bufs, rx, fading)
     if ilv is not None:
         ilv.deinterleave(rx, out=out)
 
@@ -261,7 +270,12 @@ def _check_interleaver(ilv, E):
     assert ilv is None or ilv.E == E, "the interleaver's E = %d must be the transmitted length %d" % (ilv.E, E)
 
 
-def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm, modem=None, ilv=None):
+def _check_fading(fading, modem):
+    assert fading is None or modem is not None, \
+        "fading needs a modulation: the block-fading channel carries QAM symbols (QPSK is the 1-bit-per-axis case)"
+
+
+def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm, modem=None, ilv=None, fading=None):
     """polar_round_fn's rate-matched chain; see there."""
     import torch
     from .. import _native
@@ -284,7 +298,7 @@ def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm, modem=None, 
         _polar_messages(msg, s, offset, K, crc_polynomial)
         _native.polar_encode(decoder.plan, msg, cw)
         rm.select(cw, out=tx)
-        _channel(modem, ilv, tx, E, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, rx)
+        _channel(modem, ilv, tx, E, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, rx, fading)
         rm.recover(rx, out=llr)
         decoder.plan.decode(llr, out)
         counts = torch.zeros(3, dtype=torch.int64, device="cuda")
@@ -295,7 +309,7 @@ def _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rm, modem=None, 
 
 
 def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None, rate_matcher=None, modulation=None,
-                   interleaver=None):
+                   interleaver=None, fading=None):
     """Round function for a drop-in SC/SCL decoder (polar.SCDecoder/SCLDecoder).
     Random K-bit messages (CRC appended when crc_polynomial is given, as
     src/polar/encoder.py:74-78 does), device polar encoder, device AWGN,
@@ -317,9 +331,17 @@ def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None,
     interleaver = a channel.BitInterleaver whose E is the transmitted length (the
     matcher's E, or N): the chain becomes select, interleave, channel (BPSK or
     QAM), deinterleave, recover (include/polarldpc.h at pl_interleave_check).
-    None: every call, seed and buffer as before."""
+    None: every call, seed and buffer as before.
+
+    fading = a coherence length in symbols (1 .. 2^30; 2^30 is quasi-static): the
+    QAM symbols cross block Rayleigh fading, modem.rayleigh then modem.demap_csi
+    with the coefficients known at the receiver (include/polarldpc.h at
+    pl_qam_fading_check), seed and offset as the AWGN call's.  It needs a
+    modulation.  None: every count as before."""
+    _check_fading(fading, modulation)
     if rate_matcher is not None:
-        return _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rate_matcher, modulation, interleaver)
+        return _polar_rate_matched_round_fn(decoder, seed, crc_polynomial, rate_matcher, modulation, interleaver,
+                                            fading)
     import torch
     from .. import _native
     N, K = decoder.N, decoder._n_info
@@ -343,7 +365,7 @@ def polar_round_fn(decoder, seed: int = 0, crc_polynomial: Optional[str] = None,
             _native.random_bits(s, offset, msg)
             _native.crc_append(msg, K - L, L, CRC_POLYNOMIALS[name])
         _native.polar_encode(decoder.plan, msg, cw)
-        _channel(modulation, interleaver, cw, N, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, llr)
+        _channel(modulation, interleaver, cw, N, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, llr, fading)
         decoder.plan.decode(llr, out)
         counts = torch.zeros(3, dtype=torch.int64, device="cuda")
         _native.count_errors(msg, out, K, counts)
@@ -360,7 +382,7 @@ def _plan_decode(decoder, llr, out, its):
     decoder.plan.decode(llr, out, its)
 
 
-def _rate_matched_round_fn(decoder, seed, encoder, rm, modem=None, ilv=None):
+def _rate_matched_round_fn(decoder, seed, encoder, rm, modem=None, ilv=None, fading=None):
     """ldpc_round_fn's rate-matched chain; see there."""
     import torch
     from .. import _native
@@ -398,7 +420,7 @@ def _rate_matched_round_fn(decoder, seed, encoder, rm, modem=None, ilv=None):
             msg[:, kf:] = 0  # the fillers are known zeros
             encoder.encode_batch_device(msg, out=cw)
             rm.select(cw, out=tx)
-            _channel(modem, ilv, tx, E, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, rx)
+            _channel(modem, ilv, tx, E, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, rx, fading)
             ref = msg
         rm.recover(rx, out=llr)
         _plan_decode(decoder, llr, out, its)
@@ -409,7 +431,7 @@ def _rate_matched_round_fn(decoder, seed, encoder, rm, modem=None, ilv=None):
 
 
 def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encoder=None, rate_matcher=None,
-                  modulation=None, interleaver=None):
+                  modulation=None, interleaver=None, fading=None):
     """Round function for BPDecoder / MSDecoder / LayeredMSDecoder (any decoder
     with `.plan`, `.n` and `.m`).  A QCFixedMSDecoder takes the same chain: the
     channel LLRs (and the recovery) stay fp64 and the decoder quantises them.
@@ -439,14 +461,19 @@ def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encod
     matcher's E, or n): select, interleave, channel, deinterleave (in the dtype
     the channel wrote), recover.  The all-zero codeword shortcut transmits no
     bits to interleave, so `encoder` is required here too.  None: every call as
-    before."""
+    before.
+
+    fading = a coherence length in symbols: block Rayleigh fading of the QAM
+    symbols with channel state at the demapper (polar_round_fn has the details);
+    it needs a modulation.  None: every count as before."""
+    _check_fading(fading, modulation)
     assert modulation is None or encoder is not None, \
         "modulation needs an encoder: the bit channels of a QAM symbol are not symmetric, so the all-zero " \
         "codeword shortcut is invalid"
     assert interleaver is None or encoder is not None, \
         "interleaver needs an encoder: the all-zero codeword shortcut transmits no bits to interleave"
     if rate_matcher is not None:
-        return _rate_matched_round_fn(decoder, seed, encoder, rate_matcher, modulation, interleaver)
+        return _rate_matched_round_fn(decoder, seed, encoder, rate_matcher, modulation, interleaver, fading)
     import torch
     from .. import _native
     from ..channel.awgn import AWGNChannel
@@ -479,7 +506,7 @@ def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encod
         else:
             _native.random_bits(s, offset, msg)
             encoder.encode_batch_device(msg, out=cw)
-            _channel(modulation, interleaver, cw, n, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, llr)
+            _channel(modulation, interleaver, cw, n, nframes, snr_db, s ^ 0xA5A5A5A5, offset, bufs, llr, fading)
             _plan_decode(decoder, llr, out, its)
             _native.count_errors(msg, out.index_select(1, info).contiguous(), k, counts)
         return counts.cpu().numpy()
