@@ -893,6 +893,58 @@ int pl_qam_demap_csi(int32_t m, int64_t E, int64_t coherence, int64_t batch, con
                      const double* h_dev, int64_t ld_h, double snr_db, void* llr_dev, int64_t ld_llr,
                      int32_t flags, void* stream);
 
+/* ---- The exact log-MAP soft demapper ---------------------------------------------------
+ * Max-log keeps one nearest level per bit hypothesis; the a-posteriori LLR of a bit sums
+ * over all levels: log sum_{bit = 0} e^(-W d_a) - log sum_{bit = 1} e^(-W d_a).  An LLR of
+ * this kind predicts its own hard-decision error probability, 1 / (1 + e^|L|), which the
+ * magnitude-consuming stages behind the demapper (normalised and fixed-point min-sum, soft
+ * combining) rely on.  This comment is the definition; the kernel (qam.hip), channel.QAMModem
+ * and the harness cite it.  It builds on the blocks at pl_qam_check and pl_qam_fading_check:
+ * their m, E, h, S, scale, levels x_a, symbol layout, sigma, w, g, r, wg.
+ * For an axis value r, a weight W and an axis bit p, exact fp64, every step one IEEE
+ * operation, no contraction:
+ *   W is w in pl_qam_demap_logmap and wg in pl_qam_demap_csi_logmap, where r = u / g exactly
+ *   as in pl_qam_demap_csi.
+ *   d_a = (r - x_a) * (r - x_a) for each of the 2^h levels, as in max-log.
+ *   For each hypothesis v in {0, 1}: D_v = min d_a over the levels whose bit p is v (max-log's
+ *   d0 and d1).  T_v starts at 0.0; over the levels of that set in ascending level index
+ *   (index 0 is the largest level: idx of the axis mapping):
+ *     q = (D_v - d_a) * W
+ *     e = expm1(q) + 1.0
+ *     T_v = T_v + e
+ *   c_v = log1p(T_v - 1.0)
+ *   llr = ((D_1 - D_0) * W) + (c_0 - c_1).  Positive decides 0.
+ * expm1 and log1p are the functions as glibc 2.35's dbl-64 libm computes them (the fdlibm
+ * algorithms with glibc's evaluation order; csrc/libm_exact.hpp restates them in plain IEEE
+ * operations), extended to expm1(-inf) = -1.0, expm1(NaN) = NaN and log1p(NaN) = NaN.  The sum
+ * is written around the minimum, so every exponent is <= 0 and nothing overflows; the
+ * form expm1 + 1 and log1p(T - 1) is chosen because those two functions are the ones whose
+ * bit-exact restatement the library already carries.
+ * Consequences:
+ *   T_v >= 1.0 always: the minimum itself contributes expm1(+-0) + 1.0 = 1.0, and every other
+ *     term is in [0, 1].  The log1p argument is therefore in [0, 2^(h-1) - 1].
+ *   g == 0.0 in pl_qam_demap_csi_logmap: every LLR of the symbol is +0.0, as in max-log.
+ *   An LLR that max-log gives as NaN (a NaN r, every d_a overflowing) is NaN here.  Every other
+ *     special value gives what the operations give: a d_a that alone overflows has q = -inf
+ *     and contributes e = 0.0.  A NaN's payload is unspecified.
+ *   QPSK, and any r, W for which every q of a non-minimal level is <= -56 ln 2 (glibc's expm1
+ *     returns -1.0 from the double 0x1.3687ap+5 on, in magnitude): T_v = 1.0, c_v = +0.0 and
+ *     the result equals max-log's as a number.  It is bit for bit equal, except that max-log's
+ *     -0.0 becomes +0.0 (-0.0 + (+0.0)).
+ *   With h = (1.0, 0.0) and finite y, pl_qam_demap_csi_logmap equals pl_qam_demap_logmap bit
+ *     for bit, as the max-log pair does.
+ *   PL_QAM_LLR_F32: the fp64 result rounded once to fp32.
+ * A kernel may skip a level whose q is <= -0x1.3687ap+5: its e is 0.0 and T_v + 0.0 is T_v. */
+/* pl_qam_demap with the exact log-MAP LLR defined above: its arguments, its refusals, its
+ * stores.  Asynchronous on `stream`; batch == 0 launches nothing; every check runs before
+ * the first device call. */
+int pl_qam_demap_logmap(int32_t m, int64_t E, int64_t batch, const double* y_dev, int64_t ld_y, double snr_db,
+                        void* llr_dev, int64_t ld_llr, int32_t flags, void* stream);
+/* pl_qam_demap_csi likewise. */
+int pl_qam_demap_csi_logmap(int32_t m, int64_t E, int64_t coherence, int64_t batch, const double* y_dev, int64_t ld_y,
+                            const double* h_dev, int64_t ld_h, double snr_db, void* llr_dev, int64_t ld_llr,
+                            int32_t flags, void* stream);
+
 /* ---- Bit interleaver between rate matching and the QAM modem ---------------------------
  * The m bit positions of a QAM symbol are unequally reliable and a rate matcher hands over
  * runs of consecutive code bits; the interleaver spreads such a run over the positions.

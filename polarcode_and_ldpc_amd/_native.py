@@ -35,7 +35,7 @@ EXPORTS = (
     "pl_debug_ldpc_qc_fixed_plan_probe", "pl_polar_rate_match_check", "pl_debug_polar_rate_match_probe",
     "pl_polar_rate_match_forced", "pl_polar_rate_match", "pl_polar_rate_recover",
     "pl_qam_check", "pl_qam_modulate", "pl_qam_awgn", "pl_qam_demap",
-    "pl_qam_fading_check", "pl_qam_rayleigh", "pl_qam_demap_csi",
+    "pl_qam_fading_check", "pl_qam_rayleigh", "pl_qam_demap_csi", "pl_qam_demap_logmap", "pl_qam_demap_csi_logmap",
     "pl_interleave_check", "pl_interleave_index", "pl_interleave_lds_max_e", "pl_bit_interleave", "pl_llr_deinterleave",
 )
 PL_QUANT_LLR_F32 = 1  # pl_llr_quantize flag: llr_dev is float (else double)
@@ -149,6 +149,8 @@ def _load(path=LIB_PATH):
     L.pl_qam_fading_check.argtypes = [I32, I64, I64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.pl_qam_rayleigh.argtypes = [I32, I64, I64, I64, P, I64, D, ctypes.c_uint64, I64, P, I64, P, I64, P]
     L.pl_qam_demap_csi.argtypes = [I32, I64, I64, I64, P, I64, P, I64, D, P, I64, I32, P]
+    L.pl_qam_demap_logmap.argtypes = L.pl_qam_demap.argtypes
+    L.pl_qam_demap_csi_logmap.argtypes = L.pl_qam_demap_csi.argtypes
     L.pl_interleave_check.argtypes = [I32, I32, I64, ctypes.POINTER(ctypes.c_int64)]
     L.pl_interleave_index.argtypes = [I32, I32, I64, I64, ctypes.POINTER(ctypes.c_int64)]
     L.pl_interleave_lds_max_e.argtypes = [I32]
@@ -589,10 +591,12 @@ def qam_awgn(m: int, E: int, e: "torch.Tensor | None", snr_db: float, seed: int,
                           _stream(stream)), "pl_qam_awgn")
 
 
-def qam_demap(m: int, E: int, y: "torch.Tensor", snr_db: float, llr: "torch.Tensor", stream=None):
-    """pl_qam_demap: y float64 [B, >= 2 S], llr float64 or float32 [B, >= E] on the device."""
-    check(lib.pl_qam_demap(int(m), int(E), y.shape[0], y.data_ptr(), _ld(y), float(snr_db), llr.data_ptr(), _ld(llr),
-                           PL_QAM_LLR_F32 if llr.dtype == torch.float32 else 0, _stream(stream)), "pl_qam_demap")
+def qam_demap(m: int, E: int, y: "torch.Tensor", snr_db: float, llr: "torch.Tensor", stream=None, logmap: bool = False):
+    """pl_qam_demap, or with logmap pl_qam_demap_logmap: y float64 [B, >= 2 S], llr float64 or float32 [B, >= E] on
+    the device."""
+    name = "pl_qam_demap_logmap" if logmap else "pl_qam_demap"
+    check(getattr(lib, name)(int(m), int(E), y.shape[0], y.data_ptr(), _ld(y), float(snr_db), llr.data_ptr(), _ld(llr),
+                             PL_QAM_LLR_F32 if llr.dtype == torch.float32 else 0, _stream(stream)), name)
 
 
 def qam_fading_check(m: int, E: int, coherence: int):
@@ -615,13 +619,13 @@ def qam_rayleigh(m: int, E: int, coherence: int, e: "torch.Tensor | None", snr_d
 
 
 def qam_demap_csi(m: int, E: int, coherence: int, y: "torch.Tensor", h: "torch.Tensor", snr_db: float,
-                  llr: "torch.Tensor", stream=None):
-    """pl_qam_demap_csi: y float64 [B, >= 2 S], h float64 [B, >= 2 Q], llr float64 or float32 [B, >= E] on the
-    device."""
-    check(lib.pl_qam_demap_csi(int(m), int(E), int(coherence), y.shape[0], y.data_ptr(), _ld(y), h.data_ptr(), _ld(h),
-                               float(snr_db), llr.data_ptr(), _ld(llr),
-                               PL_QAM_LLR_F32 if llr.dtype == torch.float32 else 0, _stream(stream)),
-          "pl_qam_demap_csi")
+                  llr: "torch.Tensor", stream=None, logmap: bool = False):
+    """pl_qam_demap_csi, or with logmap pl_qam_demap_csi_logmap: y float64 [B, >= 2 S], h float64 [B, >= 2 Q], llr
+    float64 or float32 [B, >= E] on the device."""
+    name = "pl_qam_demap_csi_logmap" if logmap else "pl_qam_demap_csi"
+    check(getattr(lib, name)(int(m), int(E), int(coherence), y.shape[0], y.data_ptr(), _ld(y), h.data_ptr(), _ld(h),
+                             float(snr_db), llr.data_ptr(), _ld(llr),
+                             PL_QAM_LLR_F32 if llr.dtype == torch.float32 else 0, _stream(stream)), name)
 
 
 # the largest E the interleaver kernels permute in LDS, by element size in bytes; longer frames go the direct way

@@ -1,4 +1,4 @@
-"""Gray-mapped square QAM: modulator, complex AWGN, max-log soft demapper.
+"""Gray-mapped square QAM: modulator, complex AWGN, max-log and exact log-MAP soft demappers.
 
 QAMModem(bits_per_symbol) stands between a rate matcher's E transmitted bits and
 the E LLRs it takes back: QPSK, 16-, 64- and 256-QAM (BPSK stays with
@@ -12,6 +12,10 @@ and give NumPy back, or CUDA tensors in and out with no host copy.
 Block Rayleigh fading of the symbols with channel state at the demapper (the
 definition: include/polarldpc.h at pl_qam_fading_check) rides on it: rayleigh /
 demap_csi on the device, fade_host / demap_csi_host as the definition in NumPy.
+
+The demapper is max-log by default; QAMModem(m, demapper="logmap"), or method="logmap" at a call, gives the
+exact log-MAP LLR (the definition: include/polarldpc.h at pl_qam_demap_logmap), on the device and in the host
+methods alike; its expm1 and log1p are glibc's algorithms restated in libm_np.
 """
 from __future__ import annotations
 
@@ -20,8 +24,10 @@ import math
 import numpy as np
 
 from .. import _native
+from . import libm_np
 
 NAMES = {"qpsk": 2, "16qam": 4, "64qam": 6, "256qam": 8}
+DEMAPPERS = ("maxlog", "logmap")
 
 
 def sigma_of(snr_db: float) -> float:
@@ -31,10 +37,13 @@ def sigma_of(snr_db: float) -> float:
 
 class QAMModem:
     """m = bits_per_symbol in {2, 4, 6, 8}; h = m / 2 bits per axis.  AssertionError names the condition
-    violated (include/polarldpc.h, pl_qam_check).  Construction makes no device call."""
+    violated (include/polarldpc.h, pl_qam_check).  demapper: "maxlog" or "logmap", what demap, demap_csi and their
+    host forms compute when their `method` is None.  Construction makes no device call."""
 
-    def __init__(self, bits_per_symbol: int):
+    def __init__(self, bits_per_symbol: int, demapper: str = "maxlog"):
         _, self.scale = _native.qam_check(bits_per_symbol, 1)
+        assert demapper in DEMAPPERS, "demapper %r must be one of %s" % (demapper, ", ".join(DEMAPPERS))
+        self.demapper = demapper
         self.m = int(bits_per_symbol)
         self.h = self.m // 2
         L = 1 << self.h
@@ -51,6 +60,31 @@ class QAMModem:
         c = np.bitwise_xor.accumulate(b.astype(np.int64) & 1, axis=-1)
         idx = (c << np.arange(self.h - 1, -1, -1)).sum(axis=-1)
         return ((1 << self.h) - 1) - 2 * idx
+
+    def _method(self, method) -> str:
+        """a call's method: None is the modem's own demapper"""
+        if method is None:
+            return self.demapper
+        assert method in DEMAPPERS, "demapper %r must be one of %s" % (method, ", ".join(DEMAPPERS))
+        return method
+
+    def _axis_llrs(self, d, W, logmap: bool) -> np.ndarray:
+        """d [B, S, axis, level], W a scalar or [B, S, 1] -> [B, S, h, axis]: max-log, or the exact log-MAP of
+        pl_qam_demap_logmap, the levels of each set in ascending index"""
+        out = np.empty(d.shape[:2] + (self.h, 2), dtype=np.float64)
+        for p in range(self.h):
+            one = self.level_bits[:, p] == 1
+            D1, D0 = d[..., one].min(axis=-1), d[..., ~one].min(axis=-1)
+            out[:, :, p, :] = (D1 - D0) * W
+            if logmap:
+                c = []
+                for D, idx in ((D0, np.flatnonzero(~one)), (D1, np.flatnonzero(one))):
+                    T = np.zeros_like(D)
+                    for a in idx:
+                        T = T + (libm_np.expm1((D - d[..., a]) * W) + 1.0)
+                    c.append(libm_np.log1p(T - 1.0))
+                out[:, :, p, :] = out[:, :, p, :] + (c[0] - c[1])
+        return out
 
     def S(self, E: int) -> int:
         """symbols per frame of E transmitted bits"""
@@ -69,8 +103,10 @@ class QAMModem:
         x = (a.astype(np.float64) * np.float64(self.scale)).reshape(-1, 2 * S)
         return x[0] if bits.ndim == 1 else x
 
-    def demap_host(self, y, E: int, snr_db: float, dtype=np.float64) -> np.ndarray:
-        """y float64 [B, >= 2 S] (or [2 S]) -> LLRs [B, E] (or [E]) of `dtype` (float64 or float32)."""
+    def demap_host(self, y, E: int, snr_db: float, dtype=np.float64, method=None) -> np.ndarray:
+        """y float64 [B, >= 2 S] (or [2 S]) -> LLRs [B, E] (or [E]) of `dtype` (float64 or float32); method: None
+        (the modem's demapper), "maxlog" or "logmap"."""
+        logmap = self._method(method) == "logmap"
         y = np.asarray(y, dtype=np.float64)
         y2 = np.atleast_2d(y)
         S = self.S(E)
@@ -82,10 +118,7 @@ class QAMModem:
         with np.errstate(over="ignore", invalid="ignore"):
             t = r[..., None] - self.level_values
             d = t * t  # [B, S, axis, level]
-            out = np.empty((r.shape[0], S, self.h, 2), dtype=np.float64)
-            for p in range(self.h):
-                one = self.level_bits[:, p] == 1
-                out[:, :, p, :] = (d[..., one].min(axis=-1) - d[..., ~one].min(axis=-1)) * w
+            out = self._axis_llrs(d, w, logmap)
             llr = out.reshape(-1, S * self.m)[:, :E].astype(np.dtype(dtype))
         return llr[0] if y.ndim == 1 else llr
 
@@ -129,12 +162,14 @@ class QAMModem:
             _native.qam_awgn(self.m, E, e, snr_db, seed, frame_offset, y, stream=stream)
         return y.cpu().numpy() if host and out is None else y
 
-    def demap(self, y, E: int, snr_db: float, dtype=np.float64, out=None, stream=None):
-        """Max-log LLRs on the device (pl_qam_demap): y float64 [B, >= 2 S] CUDA tensor (unit inner stride, any row
+    def demap(self, y, E: int, snr_db: float, dtype=np.float64, out=None, stream=None, method=None):
+        """LLRs on the device, max-log (pl_qam_demap) or exact log-MAP (pl_qam_demap_logmap) by `method` (None: the
+        modem's demapper): y float64 [B, >= 2 S] CUDA tensor (unit inner stride, any row
         pitch) -> [B, E] CUDA tensor of `dtype` (float64 or float32), `out` if given (its dtype counts; any row
         pitch >= E; elements beyond E stay untouched).  A NumPy array goes to the device and comes back as
         NumPy."""
         import torch
+        logmap = self._method(method) == "logmap"
         host = not isinstance(y, torch.Tensor)
         r = torch.from_numpy(np.array(y, dtype=np.float64)).cuda() if host else y
         E = int(E)
@@ -149,7 +184,7 @@ class QAMModem:
         self._check_out(llr, r.shape[0], E, llr.dtype if out is not None else tdt, "out", "E")
         assert llr.dtype in (torch.float32, torch.float64), "out must be float64 or float32"
         if r.shape[0]:
-            _native.qam_demap(self.m, E, r, snr_db, llr, stream=stream)
+            _native.qam_demap(self.m, E, r, snr_db, llr, stream=stream, logmap=logmap)
         return llr.cpu().numpy() if host and out is None else llr
 
     # ---- block Rayleigh fading; the definition: include/polarldpc.h at pl_qam_fading_check ----
@@ -177,9 +212,11 @@ class QAMModem:
             y[:, 1::2] = (hr * xq + hi * xi) + n2[:, 1::2]
         return y[0] if x.ndim == 1 else y
 
-    def demap_csi_host(self, y, h, E: int, snr_db: float, coherence: int = 1, dtype=np.float64) -> np.ndarray:
+    def demap_csi_host(self, y, h, E: int, snr_db: float, coherence: int = 1, dtype=np.float64,
+                       method=None) -> np.ndarray:
         """y float64 [B, >= 2 S], h float64 [B, >= 2 Q] (or one frame of each) -> LLRs [B, E] (or [E]) of `dtype`
-        (float64 or float32); a symbol whose |h|^2 is 0.0 gives +0.0."""
+        (float64 or float32); a symbol whose |h|^2 is 0.0 gives +0.0; method as demap_host's."""
+        logmap = self._method(method) == "logmap"
         y = np.asarray(y, dtype=np.float64)
         y2 = np.atleast_2d(y)
         S = _native.qam_fading_check(self.m, E, coherence)[0]
@@ -197,10 +234,7 @@ class QAMModem:
             wg = (w * g)[..., None]
             t = r[..., None] - self.level_values
             d = t * t  # [B, S, axis, level]
-            out = np.empty((r.shape[0], S, self.h, 2), dtype=np.float64)
-            for p in range(self.h):
-                one = self.level_bits[:, p] == 1
-                out[:, :, p, :] = (d[..., one].min(axis=-1) - d[..., ~one].min(axis=-1)) * wg
+            out = self._axis_llrs(d, wg, logmap)
             out[g == 0.0] = 0.0
             llr = out.reshape(-1, S * self.m)[:, :E].astype(np.dtype(dtype))
         return llr[0] if y.ndim == 1 else llr
@@ -232,12 +266,15 @@ class QAMModem:
             return (y.cpu().numpy() if out is None else y), (h.cpu().numpy() if h_out is None else h)
         return y, h
 
-    def demap_csi(self, y, h, E: int, snr_db: float, coherence: int = 1, dtype=np.float64, out=None, stream=None):
-        """Max-log LLRs with channel state on the device (pl_qam_demap_csi): y float64 [B, >= 2 S] and h float64
+    def demap_csi(self, y, h, E: int, snr_db: float, coherence: int = 1, dtype=np.float64, out=None, stream=None,
+                  method=None):
+        """LLRs with channel state on the device, max-log (pl_qam_demap_csi) or exact log-MAP
+        (pl_qam_demap_csi_logmap) by `method` (None: the modem's demapper): y float64 [B, >= 2 S] and h float64
         [B, >= 2 Q], CUDA tensors (unit inner stride, any row pitch) -> [B, E] CUDA tensor of `dtype` (float64 or
         float32), `out` if given (its dtype counts; any row pitch >= E; elements beyond E stay untouched).  NumPy
         arrays go to the device and the result comes back as NumPy."""
         import torch
+        logmap = self._method(method) == "logmap"
         host = not isinstance(y, torch.Tensor)
         r = torch.from_numpy(np.array(y, dtype=np.float64)).cuda() if host else y
         c = torch.from_numpy(np.array(h, dtype=np.float64)).cuda() if not isinstance(h, torch.Tensor) else h
@@ -257,7 +294,7 @@ class QAMModem:
         self._check_out(llr, r.shape[0], E, llr.dtype if out is not None else tdt, "out", "E")
         assert llr.dtype in (torch.float32, torch.float64), "out must be float64 or float32"
         if r.shape[0]:
-            _native.qam_demap_csi(self.m, E, coherence, r, c, snr_db, llr, stream=stream)
+            _native.qam_demap_csi(self.m, E, coherence, r, c, snr_db, llr, stream=stream, logmap=logmap)
         return llr.cpu().numpy() if host and out is None else llr
 
     @staticmethod
@@ -267,4 +304,6 @@ class QAMModem:
             "%s must be a [B, %s = %d] device tensor of %s, rows apart" % (name, what, width, dtype)
 
     def __repr__(self) -> str:
+        if self.demapper != "maxlog":
+            return "QAMModem(bits_per_symbol=%d, demapper=%r)" % (self.m, self.demapper)
         return "QAMModem(bits_per_symbol=%d)" % self.m

@@ -1454,8 +1454,9 @@ extern "C" int pl_qam_awgn(int32_t m, int64_t E, int64_t batch, const uint8_t* e
     return err == hipSuccess ? PL_OK : hipfail(err, "qam awgn launch");
 }
 
-extern "C" int pl_qam_demap(int32_t m, int64_t E, int64_t batch, const double* y, int64_t ld_y, double snr_db,
-                            void* llr, int64_t ld_llr, int32_t flags, void* stream) {
+// pl_qam_demap and pl_qam_demap_logmap: one argument list, one set of refusals, the kernel by `logmap`
+static int qam_demap_call(bool logmap, int32_t m, int64_t E, int64_t batch, const double* y, int64_t ld_y,
+                          double snr_db, void* llr, int64_t ld_llr, int32_t flags, void* stream) {
     int64_t S;
     double scale, sigma;
     if (int rc = qam_args(m, E, batch, &S, &scale)) return rc;
@@ -1468,9 +1469,22 @@ extern "C" int pl_qam_demap(int32_t m, int64_t E, int64_t batch, const double* y
     if (ld_llr < E) return fail(PL_EINVAL, "ld_llr < E = " + std::to_string(E));
     const double s2 = sigma * sigma;
     const double w = 1.0 / (2.0 * s2);
-    const hipError_t err = pl::qam_demap_launch(m, E, S, scale, y, ld_y, batch, w, llr, ld_llr, flags & PL_QAM_LLR_F32,
-                                                (hipStream_t)stream);
-    return err == hipSuccess ? PL_OK : hipfail(err, "qam demap launch");
+    const hipError_t err =
+        logmap ? pl::qam_demap_logmap_launch(m, E, S, 1, scale, y, ld_y, nullptr, 0, batch, w, llr, ld_llr,
+                                             flags & PL_QAM_LLR_F32, (hipStream_t)stream)
+               : pl::qam_demap_launch(m, E, S, scale, y, ld_y, batch, w, llr, ld_llr, flags & PL_QAM_LLR_F32,
+                                      (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, logmap ? "qam demap logmap launch" : "qam demap launch");
+}
+
+extern "C" int pl_qam_demap(int32_t m, int64_t E, int64_t batch, const double* y, int64_t ld_y, double snr_db,
+                            void* llr, int64_t ld_llr, int32_t flags, void* stream) {
+    return qam_demap_call(false, m, E, batch, y, ld_y, snr_db, llr, ld_llr, flags, stream);
+}
+
+extern "C" int pl_qam_demap_logmap(int32_t m, int64_t E, int64_t batch, const double* y, int64_t ld_y, double snr_db,
+                                   void* llr, int64_t ld_llr, int32_t flags, void* stream) {
+    return qam_demap_call(true, m, E, batch, y, ld_y, snr_db, llr, ld_llr, flags, stream);
 }
 
 // ---- block Rayleigh fading for the QAM symbols (qam.hip); the definition: include/polarldpc.h, pl_qam_fading_check ----
@@ -1506,9 +1520,10 @@ extern "C" int pl_qam_rayleigh(int32_t m, int64_t E, int64_t coherence, int64_t 
     return err == hipSuccess ? PL_OK : hipfail(err, "qam rayleigh launch");
 }
 
-extern "C" int pl_qam_demap_csi(int32_t m, int64_t E, int64_t coherence, int64_t batch, const double* y, int64_t ld_y,
-                                const double* h, int64_t ld_h, double snr_db, void* llr, int64_t ld_llr, int32_t flags,
-                                void* stream) {
+// pl_qam_demap_csi and pl_qam_demap_csi_logmap, as qam_demap_call
+static int qam_demap_csi_call(bool logmap, int32_t m, int64_t E, int64_t coherence, int64_t batch, const double* y,
+                              int64_t ld_y, const double* h, int64_t ld_h, double snr_db, void* llr, int64_t ld_llr,
+                              int32_t flags, void* stream) {
     int64_t S, Q;
     double scale, sigma;
     if (int rc = pl_qam_fading_check(m, E, coherence, &S, &Q)) return rc;
@@ -1522,9 +1537,21 @@ extern "C" int pl_qam_demap_csi(int32_t m, int64_t E, int64_t coherence, int64_t
     pl::qam_check(m, E, nullptr, &scale);
     const double s2 = sigma * sigma;
     const double w = 1.0 / (2.0 * s2);
-    const hipError_t err = pl::qam_demap_csi_launch(m, E, S, coherence, scale, y, ld_y, h, ld_h, batch, w, llr, ld_llr,
-                                                    flags & PL_QAM_LLR_F32, (hipStream_t)stream);
-    return err == hipSuccess ? PL_OK : hipfail(err, "qam demap csi launch");
+    const hipError_t err = (logmap ? pl::qam_demap_logmap_launch : pl::qam_demap_csi_launch)(
+        m, E, S, coherence, scale, y, ld_y, h, ld_h, batch, w, llr, ld_llr, flags & PL_QAM_LLR_F32, (hipStream_t)stream);
+    return err == hipSuccess ? PL_OK : hipfail(err, logmap ? "qam demap csi logmap launch" : "qam demap csi launch");
+}
+
+extern "C" int pl_qam_demap_csi(int32_t m, int64_t E, int64_t coherence, int64_t batch, const double* y, int64_t ld_y,
+                                const double* h, int64_t ld_h, double snr_db, void* llr, int64_t ld_llr, int32_t flags,
+                                void* stream) {
+    return qam_demap_csi_call(false, m, E, coherence, batch, y, ld_y, h, ld_h, snr_db, llr, ld_llr, flags, stream);
+}
+
+extern "C" int pl_qam_demap_csi_logmap(int32_t m, int64_t E, int64_t coherence, int64_t batch, const double* y,
+                                       int64_t ld_y, const double* h, int64_t ld_h, double snr_db, void* llr,
+                                       int64_t ld_llr, int32_t flags, void* stream) {
+    return qam_demap_csi_call(true, m, E, coherence, batch, y, ld_y, h, ld_h, snr_db, llr, ld_llr, flags, stream);
 }
 
 // ---- the bit interleaver (interleave.hip); the definition: include/polarldpc.h, pl_interleave_check ----

@@ -198,6 +198,11 @@ hipError_t qam_rayleigh_launch(int m, int64_t E, int64_t S, int64_t Lc, double s
 hipError_t qam_demap_csi_launch(int m, int64_t E, int64_t S, int64_t Lc, double scale, const double* y, int64_t ldy,
                                 const double* h, int64_t ldh, int64_t batch, double w, void* llr, int64_t ldl,
                                 bool llr_f32, hipStream_t s);
+// The exact log-MAP demapper (the definition: include/polarldpc.h, pl_qam_demap_logmap): qam_demap_launch's
+// arguments with h == nullptr (Lc, ldh not used), qam_demap_csi_launch's otherwise.
+hipError_t qam_demap_logmap_launch(int m, int64_t E, int64_t S, int64_t Lc, double scale, const double* y, int64_t ldy,
+                                   const double* h, int64_t ldh, int64_t batch, double w, void* llr, int64_t ldl,
+                                   bool llr_f32, hipStream_t s);
 
 // ---- the bit interleaver (interleave.hip); the definition: include/polarldpc.h, pl_interleave_check ----
 // kind, p checked (ilv_check).  e, f [batch][ld], pitches in elements: uint8 for the bits, double or float

@@ -19,9 +19,13 @@
 //     and written by the block's first symbol.
 //   qam_demap_csi_kernel<H, T>: qam_demap_kernel's groups and stores; per symbol one more 16-byte load (the
 //     coefficient), five products, two divisions, and the erased symbol (|h|^2 == 0.0 -> +0.0).
+// The exact log-MAP demapper (the definition: include/polarldpc.h at pl_qam_demap_logmap) rides on the demappers:
+//   qam_demap_logmap_kernel<H, T, CSI>: their groups, loads and stores; per axis value the minima of max-log, then
+//     h 2^h expm1 and 2 h log1p as glibc computes them (libm_exact.hpp), levels and axis values in rolled loops.
 // Launches stay below 2^31 work-items (row chunks), so work-item indices are 32-bit.
 #include "common.hpp"
 #include "internal.hpp"
+#include "libm_exact.hpp"
 #include "qam_check.hpp"
 
 namespace pl {
@@ -319,6 +323,155 @@ qam_demap_csi_kernel(const double* __restrict__ y, int64_t ldy, const double* __
     qam_store_cut<V, T>(llr + (int64_t)row * ldl + t0, v, E - t0);
 }
 
+// ---- the exact log-MAP demapper; the definition: include/polarldpc.h at pl_qam_demap_logmap ----
+// glibc's expm1 and log1p (libm_exact.hpp, whose functions stay as they are) on the arguments the definition can
+// produce: q = (D_v - d_a) W is <= 0, -inf or NaN (D_v is the minimum and W >= 0 or NaN), T_v - 1.0 is in [0, 7] or NaN.
+PL_DEV double qam_expm1(double x) {
+    if (x != x) return x + x;  // NaN
+    if (x == -__builtin_inf()) return -1.0;
+    return libm_expm1(x);
+}
+
+PL_DEV double qam_log1p(double x) {
+    if (x != x) return x + x;  // NaN
+    return libm_log1p_pos(x);
+}
+
+// glibc's expm1 returns its constant (tiny - 1.0 = -1.0) from the first double whose high word is 0x4043687A on, the
+// 56 ln 2 of its comment; e is then +0.0 and T_v + 0.0 is T_v bit for bit (T_v is never -0.0: it starts at +0.0 and
+// only terms >= +0.0 are added).  A NaN q fails the comparison and takes the whole path.
+constexpr double kQamSkip = -0x1.3687ap+5;
+
+// the H minima pairs of one axis value, qam_axis_llr's d0 and d1
+template <int H>
+PL_DEV void qam_axis_minima(double r, double scale, double (&D0)[H], double (&D1)[H]) {
+    constexpr int L = 1 << H;
+    double d[L];
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+        const double t = r - (double)((L - 1) - 2 * i) * scale;
+        d[i] = t * t;
+    }
+#pragma unroll
+    for (int p = 0; p < H; ++p) {
+        double d0 = d[0], d1 = d[1 << (H - 1 - p)];
+#pragma unroll
+        for (int i = 1; i < L; ++i) {
+            if (((i ^ (i >> 1)) >> (H - 1 - p)) & 1) {
+                if (i != (1 << (H - 1 - p))) d1 = __builtin_fmin(d1, d[i]);
+            } else {
+                d0 = __builtin_fmin(d0, d[i]);
+            }
+        }
+        D0[p] = d0;
+        D1[p] = d1;
+    }
+}
+
+// the H LLRs of one axis value r at weight W.  The levels run in a rolled loop in ascending index, so that the
+// kernel holds H copies of expm1 and not H 2^H: level i's distance is computed again (the same two operations give
+// the same double) and goes to T_0 or T_1 of each bit by the bit the level carries there.  The sums sit in 2 H
+// registers whatever the level count.
+template <int H>
+PL_DEV void qam_axis_llr_logmap(double r, double scale, double W, double (&llr)[H]) {
+    constexpr int L = 1 << H;
+    double D0[H], D1[H], T0[H], T1[H];
+    qam_axis_minima<H>(r, scale, D0, D1);
+#pragma unroll
+    for (int p = 0; p < H; ++p) T0[p] = T1[p] = 0.0;
+#pragma unroll 1
+    for (int i = 0; i < L; ++i) {
+        const double t = r - (double)((L - 1) - 2 * i) * scale;
+        const double d = t * t;
+        const int gray = i ^ (i >> 1);
+#pragma unroll
+        for (int p = 0; p < H; ++p) {
+            const bool one = (gray >> (H - 1 - p)) & 1;
+            const double q = ((one ? D1[p] : D0[p]) - d) * W;
+            if (!(q <= kQamSkip)) {
+                const double e = qam_expm1(q) + 1.0;
+                const double s0 = T0[p] + e, s1 = T1[p] + e;
+                T0[p] = one ? T0[p] : s0;
+                T1[p] = one ? s1 : T1[p];
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < H; ++p) {
+        const double c0 = qam_log1p(T0[p] - 1.0), c1 = qam_log1p(T1[p] - 1.0);
+        llr[p] = ((D1[p] - D0[p]) * W) + (c0 - c1);
+    }
+}
+
+// qam_demap_kernel's and qam_demap_csi_kernel's groups, loads and stores (CSI: with the channel state) around the
+// log-MAP arithmetic.  The 2 G axis values of a group go through one copy of that arithmetic, in a rolled loop
+// whose counter is uniform over the wave: the selects in front of it and behind it compare that counter with
+// constants, and v stays in registers.
+template <int H, typename T, bool CSI>
+__global__ void __launch_bounds__(kQamThreads)
+qam_demap_logmap_kernel(const double* __restrict__ y, int64_t ldy, const double* __restrict__ h, int64_t ldh, uint32_t E,
+                        uint32_t S, uint32_t Lc, uint32_t W, uint32_t total, double scale, double w,
+                        T* __restrict__ llr, int64_t ldl) {
+    constexpr uint32_t M = 2 * H;
+    constexpr uint32_t G = (sizeof(T) == 4 && (H & 1)) ? 2 : 1;
+    constexpr uint32_t V = G * M;
+    static_assert(V % (16 / sizeof(T)) == 0, "a group is whole 16-byte pieces");
+    const uint32_t idx = blockIdx.x * kQamThreads + threadIdx.x;
+    if (idx >= total) return;
+    const uint32_t row = idx / W, g = idx - row * W;
+    const double* src = y + (int64_t)row * ldy;
+    double r[2 * G], wt[G];
+    bool erased[G];
+#pragma unroll
+    for (uint32_t k = 0; k < G; ++k) {
+        const uint32_t s = g * G + k;
+        double yi = 0.0, yq = 0.0, hr = 1.0, hi = 0.0;  // a symbol behind S: its LLRs are not stored
+        if (s < S) {
+            qam_load2(src + 2 * (int64_t)s, yi, yq);
+            if (CSI) qam_load2(h + (int64_t)row * ldh + 2 * (int64_t)(s / Lc), hr, hi);
+        }
+        if (CSI) {
+            const double g2 = hr * hr + hi * hi;
+            const double ui = hr * yi + hi * yq;
+            const double uq = hr * yq - hi * yi;
+            r[2 * k] = ui / g2;
+            r[2 * k + 1] = uq / g2;
+            wt[k] = w * g2;
+            erased[k] = g2 == 0.0;
+        } else {
+            r[2 * k] = yi;
+            r[2 * k + 1] = yq;
+            wt[k] = w;
+            erased[k] = false;
+        }
+    }
+    T v[V];
+#pragma unroll 1
+    for (uint32_t a = 0; a < 2 * G; ++a) {
+        double ra = r[0], wa = wt[0];
+        bool er = erased[0];
+#pragma unroll
+        for (uint32_t j = 1; j < 2 * G; ++j) {
+            if (a == j) {
+                ra = r[j];
+                wa = wt[j / 2];
+                er = erased[j / 2];
+            }
+        }
+        double l[H];
+        qam_axis_llr_logmap<H>(ra, scale, wa, l);
+#pragma unroll
+        for (uint32_t j = 0; j < 2 * G; ++j) {
+            if (a == j) {
+#pragma unroll
+                for (int p = 0; p < H; ++p) v[(j / 2) * M + 2 * p + (j & 1)] = er ? (T)0.0 : (T)l[p];
+            }
+        }
+    }
+    const uint32_t t0 = g * V;  // < E: W = ceil(E / V)
+    qam_store_cut<V, T>(llr + (int64_t)row * ldl + t0, v, E - t0);
+}
+
 // rows of W work-items each, in launches below 2^31 work-items; fn(first row, work-items)
 template <class Launch>
 static hipError_t qam_chunks(int64_t batch, int64_t W, Launch fn) {
@@ -452,6 +605,43 @@ hipError_t qam_demap_csi_launch(int m, int64_t E, int64_t S, int64_t Lc, double 
     if (batch == 0) return hipSuccess;
     return llr_f32 ? qam_demap_csi_m(m, E, S, Lc, scale, y, ldy, h, ldh, batch, w, (float*)llr, ldl, s)
                    : qam_demap_csi_m(m, E, S, Lc, scale, y, ldy, h, ldh, batch, w, (double*)llr, ldl, s);
+}
+
+template <int H, typename T, bool CSI>
+static hipError_t qam_demap_logmap(int64_t E, int64_t S, int64_t Lc, double scale, const double* y, int64_t ldy,
+                                   const double* h, int64_t ldh, int64_t batch, double w, T* llr, int64_t ldl,
+                                   hipStream_t st) {
+    constexpr int64_t V = ((sizeof(T) == 4 && (H & 1)) ? 2 : 1) * 2 * H;
+    const int64_t W = (E + V - 1) / V;
+    return qam_chunks(batch, W, [&](int64_t b0, uint32_t total) {
+        hipLaunchKernelGGL((qam_demap_logmap_kernel<H, T, CSI>), dim3((total + kQamThreads - 1) / kQamThreads),
+                           dim3(kQamThreads), 0, st, y + b0 * ldy, ldy, CSI ? h + b0 * ldh : h, ldh, (uint32_t)E,
+                           (uint32_t)S, (uint32_t)Lc, (uint32_t)W, total, scale, w, llr + b0 * ldl, ldl);
+        return hipGetLastError();
+    });
+}
+
+template <typename T, bool CSI>
+static hipError_t qam_demap_logmap_m(int m, int64_t E, int64_t S, int64_t Lc, double scale, const double* y,
+                                     int64_t ldy, const double* h, int64_t ldh, int64_t batch, double w, T* llr,
+                                     int64_t ldl, hipStream_t st) {
+    switch (m) {
+        case 2: return qam_demap_logmap<1, T, CSI>(E, S, Lc, scale, y, ldy, h, ldh, batch, w, llr, ldl, st);
+        case 4: return qam_demap_logmap<2, T, CSI>(E, S, Lc, scale, y, ldy, h, ldh, batch, w, llr, ldl, st);
+        case 6: return qam_demap_logmap<3, T, CSI>(E, S, Lc, scale, y, ldy, h, ldh, batch, w, llr, ldl, st);
+        default: return qam_demap_logmap<4, T, CSI>(E, S, Lc, scale, y, ldy, h, ldh, batch, w, llr, ldl, st);
+    }
+}
+
+hipError_t qam_demap_logmap_launch(int m, int64_t E, int64_t S, int64_t Lc, double scale, const double* y, int64_t ldy,
+                                   const double* h, int64_t ldh, int64_t batch, double w, void* llr, int64_t ldl,
+                                   bool llr_f32, hipStream_t s) {
+    if (batch == 0) return hipSuccess;
+    if (h)
+        return llr_f32 ? qam_demap_logmap_m<float, true>(m, E, S, Lc, scale, y, ldy, h, ldh, batch, w, (float*)llr, ldl, s)
+                       : qam_demap_logmap_m<double, true>(m, E, S, Lc, scale, y, ldy, h, ldh, batch, w, (double*)llr, ldl, s);
+    return llr_f32 ? qam_demap_logmap_m<float, false>(m, E, S, 1, scale, y, ldy, h, 0, batch, w, (float*)llr, ldl, s)
+                   : qam_demap_logmap_m<double, false>(m, E, S, 1, scale, y, ldy, h, 0, batch, w, (double*)llr, ldl, s);
 }
 
 }  // namespace pl

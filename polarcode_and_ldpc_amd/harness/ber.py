@@ -63,6 +63,11 @@ def _interleaver(interleaver, E, modulation):
     return interleaver
 
 
+def _demapper_key(modulation):
+    """the run key's "demapper": present only for a modem whose demapper is not the default max-log"""
+    return {"demapper": modulation.demapper} if modulation.demapper != "maxlog" else {}
+
+
 def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: int, config: Dict,
                    list_size: int = 0, crc_polynomial: Optional[str] = None, batch: int = 65536, seed: int = 0,
                    group=None, log_path=None, rate_match=None, modulation=None, interleaver=None, fading=None):
@@ -80,7 +85,9 @@ def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: i
 
     modulation: None (BPSK), or a channel.QAMModem: the transmitted bits cross the
     channel as Gray-mapped QAM symbols (polar_round_fn's modulation) and snr_db is
-    Es/N0 per QAM symbol; its bits per symbol enter the run key only when given.
+    Es/N0 per QAM symbol; its bits per symbol enter the run key only when given.  A modem
+    built with demapper="logmap" demaps with the exact log-MAP LLR, and "demapper" enters
+    the run key only then.
 
     interleaver: None, a channel.BitInterleaver of the transmitted length (E, or N
     without rate matching) or a (kind, rows) pair to build one there (rows None:
@@ -105,7 +112,7 @@ def simulate_polar(snr_db_range: Sequence[float], num_frames: int, max_errors: i
         fr = PolarLibWrapper(N, K, 2.0).get_frozen_bits_positions()
     kw = {}
     if modulation is not None:
-        more = dict(more, modulation=modulation.m)
+        more = dict(more, modulation=modulation.m, **_demapper_key(modulation))
         kw["modulation"] = modulation
     if interleaver is not None:
         kw["interleaver"] = _interleaver(interleaver, rm.E if rm is not None else N, modulation)
@@ -191,6 +198,7 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
     kw = {}
     if modulation is not None:
         more["modulation"] = modulation.m
+        more.update(_demapper_key(modulation))
         kw["modulation"] = modulation
     if fading is not None:
         more["fading"] = kw["fading"] = int(fading)
@@ -307,6 +315,8 @@ def main(argv=None):
     ap.add_argument("--modulation", choices=["qpsk", "16qam", "64qam", "256qam"], default=None,
                     help="--code polar, qcldpc: Gray-mapped QAM (channel.QAMModem) instead of BPSK; --snr is then Es/N0 "
                          "per QAM symbol; qcldpc needs --ldpc-codewords random")
+    ap.add_argument("--demapper", choices=["maxlog", "logmap"], default=None,
+                    help="with --modulation: the soft demapper, max-log (the default) or the exact log-MAP LLR")
     ap.add_argument("--interleave", choices=["rect", "tri"], default=None,
                     help="--code polar, qcldpc: a bit interleaver (channel.BitInterleaver) between rate matching and "
                          "the channel: row-column or triangular; qcldpc needs --ldpc-codewords random")
@@ -332,11 +342,13 @@ def main(argv=None):
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     snr = _parse_range(a.snr)
     mod = {}
+    if a.demapper is not None and a.modulation is None:
+        ap.error("--demapper needs --modulation")
     if a.modulation is not None and not a.cpu_stub:
         if a.code == "ldpc":
             ap.error("--modulation goes with --code polar or qcldpc")
         from ..channel.qam import NAMES, QAMModem
-        mod["modulation"] = QAMModem(NAMES[a.modulation])
+        mod["modulation"] = QAMModem(NAMES[a.modulation], demapper=a.demapper or "maxlog")
     if a.fading is not None:
         if a.fading != "frame" and not a.fading.isdigit():
             ap.error("--fading takes a coherence length in symbols, or 'frame'")
@@ -355,7 +367,8 @@ def main(argv=None):
     if a.cpu_stub:
         from .montecarlo import stub_round_fn
         mc = MonteCarlo(stub_round_fn(seed=7, info_bits=a.K), info_bits=a.K, batch=a.batch)
-        log = _log(a.log, mc, code="stub", K=a.K, frames=a.frames, max_errors=a.max_errors)
+        log = _log(a.log, mc, code="stub", K=a.K, frames=a.frames, max_errors=a.max_errors,
+                   **({"demapper": a.demapper} if a.demapper == "logmap" else {}))
         pts = mc.run(snr, a.frames, a.max_errors, log=log)
         ber, fer = np.array([p.ber for p in pts]), np.array([p.fer for p in pts])
     elif a.code == "polar":

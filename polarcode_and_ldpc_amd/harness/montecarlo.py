@@ -227,7 +227,8 @@ def _qam_channel(modem, bits, E, nframes, snr_db, seed, offset, bufs, rx, fading
     """The chains' channel with a channel.QAMModem: the E transmitted bits of each frame through modem.awgn
     (seed and frame offset as the BPSK call's) and modem.demap into rx [nframes, E], whose dtype the next
     stage reads.  The symbols live in bufs["sym"].  With fading, a coherence length in symbols, modem.rayleigh
-    and modem.demap_csi instead, same seed and offset; the coefficients live in bufs["csi"]."""
+    and modem.demap_csi instead, same seed and offset; the coefficients live in bufs["csi"].  The demapper is the
+    modem's own (QAMModem's demapper: max-log, or the exact log-MAP)."""
     import torch
     S2 = 2 * modem.S(E)
     if "sym" not in bufs or bufs["sym"].shape[0] < nframes:
