@@ -63,7 +63,9 @@ typedef struct {
                            15 int8 fixed-point quasi-cyclic layered min-sum with its
                            state in LDS, 16 with its state in the workspace (such a
                            plan reports in fused_top the kernel instance: 8, 16 or 32
-                           inputs of a check kept in registers, 0 the two-pass form) */
+                           inputs of a check kept in registers, 0 the two-pass form),
+                           17 fp64 quasi-cyclic layered sum-product with its state in
+                           LDS, 18 with its state in the workspace */
 } pl_plan_info;
 
 /* Polar SC / SCL plan.
@@ -240,6 +242,59 @@ int pl_ldpc_qc_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shi
 int pl_ldpc_qc_fixed_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift /* [mb*nb] row-major */,
                                  const int32_t* layer_order /* [mb] or NULL */, int32_t max_iter, int32_t early_stop,
                                  int32_t norm16, int32_t llr_max, int32_t msg_max, pl_plan** out);
+
+/* fp64 quasi-cyclic layered sum-product (belief propagation) plan.  Build-defined.
+ *   The code (mb, nb, z, shift), the layers (layer_order), the position j of an
+ *   input in its check (the rank of its block column among the row's non-zero
+ *   blocks), the skipping of block rows without blocks, max_iter == 0, the
+ *   stop rule and the hard decision are exactly pl_ldpc_qc_plan_create's; the
+ *   check rule and the state differ.  Every operation below is one IEEE
+ *   binary64 operation (no FMA contraction).
+ *   clampq(x) = +0.0 if x is NaN; clip if x > clip; -clip if x < -clip; else x.
+ *   boxplus(a, b), in this order:
+ *     m  = |b| < |a| ? |b| : |a|
+ *     s  = ((a < 0) != (b < 0)) ? -m : m
+ *     cp = log1p(expm1(-|a + b|) + 1.0)
+ *     cm = log1p(expm1(-|a - b|) + 1.0)
+ *     boxplus = s + (cp - cm)
+ *   with expm1 and log1p those of glibc 2.35 (dbl-64), bit for bit; their
+ *   arguments here are <= 0 and in [0, 1].
+ *     P[v] = clampq(L[v]);  every R = +0.0
+ *     for it < max_iter: for each block row in layer_order (d >= 2 blocks), for
+ *                        each of its z checks, inputs j = 0 .. d-1 by ascending
+ *                        block column:
+ *         q_j      = clampq(P[v_j] - R_j)
+ *         F_0      = q_0;      F_j = boxplus(F_(j-1), q_j)   j = 1 .. d-2
+ *         B_(d-1)  = q_(d-1);  B_j = boxplus(q_j, B_(j+1))   j = d-2 .. 1
+ *         R'_0     = B_1;      R'_(d-1) = F_(d-2)
+ *         R'_j     = boxplus(F_(j-1), B_(j+1))               0 < j < d-1
+ *         P[v_j]   = q_j + R'_j;  R_j = R'_j
+ *       (d == 2: the two inputs swap)
+ *       decoded = P <= 0; with early_stop, a frame whose every parity is even
+ *       after an iteration stops updating (iterations = it + 1)
+ *   The posterior output is P.  With the clamp every value stays finite,
+ *   |P| <= 2 clip + ln 2, so NaN and +-inf are ordinary inputs: a NaN LLR is an
+ *   erasure (+0.0), +-inf is +-clip.  Bits, iteration counts and posteriors
+ *   equal a NumPy restatement bit for bit.
+ *   Checks: pl_ldpc_qc_plan_create's in its order, with clip (finite,
+ *   0 < clip <= 2^20, else PL_EINVAL) behind the layer_order check and in front
+ *   of the PL_EUNSUPPORTED ones (a one-block row when max_iter > 0, with a
+ *   message of its own; >= 2048 blocks in a row; z > 1024).  Every argument
+ *   check runs before the first device call.
+ *   Mapping as pl_ldpc_qc_plan_create's.  State per frame: P[n] f64 at 0; at
+ *   off_r = 8 n rounded up to 16, R as [blocks][z] f64, where edge j of a layer
+ *   is slot (blocks of the earlier layers in stream order) + j and check r of
+ *   the layer is element slot z + r; state_bytes = off_r + 8 z blocks rounded
+ *   up to 16, in LDS under pl_ldpc_qc_plan_create's rules
+ *   (pl_plan_info.reserved 17), else in the workspace (18); PL_LMS_GLOBAL=1
+ *   forces the workspace.  Such a plan decodes fp64 LLRs through pl_decode,
+ *   pl_decode_ws and pl_ldpc_decode_soft, as the fp64 plan of
+ *   pl_ldpc_qc_plan_create; pl_ldpc_decode_f32 and pl_ldpc_decode_i8 return
+ *   PL_EUNSUPPORTED.  pl_plan_workspace_bytes, pl_plan_reserve and
+ *   pl_plan_release work as for any plan. */
+int pl_ldpc_qc_bp_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift /* [mb*nb] row-major */,
+                              const int32_t* layer_order /* [mb] or NULL */, int32_t max_iter, int32_t early_stop,
+                              double clip, pl_plan** out);
 
 /* Batched decode: replaces SCDecoder.decode (decoder.py:38-71),
  *   SCLDecoder.decode (:225-262), BPDecoder.decode (src/ldpc/decoder.py:124-202)
@@ -485,6 +540,21 @@ int pl_debug_ldpc_qc_fixed_plan_probe(int32_t mb, int32_t nb, int32_t z, const i
                                       const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
                                       int32_t norm16, int32_t llr_max, int32_t msg_max, int32_t lms_global,
                                       pl_ldpc_qc_fixed_plan_probe* out);
+
+/* The same for pl_ldpc_qc_bp_plan_create: the fields of pl_ldpc_qc_plan_probe
+ * (dcap and mw are 0: the rule keeps no input in registers and no check words)
+ * with clip, and off_r, the byte offset of R behind P. */
+typedef struct {
+    int32_t kernel;      /* 17 or 18, as pl_plan_info.reserved */
+    int32_t z, mb, nb, maxdc, dcap, mw, fpw, fpb, threads, lds_bytes, use_global;
+    double clip;
+    int64_t state_bytes, off_r;
+    int64_t table_len;
+    uint64_t digest;
+} pl_ldpc_qc_bp_plan_probe;
+int pl_debug_ldpc_qc_bp_plan_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                   const int32_t* layer_order, int32_t max_iter, int32_t early_stop, double clip,
+                                   int32_t lms_global, pl_ldpc_qc_bp_plan_probe* out);
 
 /* ---- Monte-Carlo frame source (replaces src/channel/awgn.py:91-112 and the
  *      message/encode loop of benchmarks/ber_simulation.py:167-177) ---------- */

@@ -37,6 +37,7 @@ EXPORTS = (
     "pl_qam_check", "pl_qam_modulate", "pl_qam_awgn", "pl_qam_demap",
     "pl_qam_fading_check", "pl_qam_rayleigh", "pl_qam_demap_csi", "pl_qam_demap_logmap", "pl_qam_demap_csi_logmap",
     "pl_interleave_check", "pl_interleave_index", "pl_interleave_lds_max_e", "pl_bit_interleave", "pl_llr_deinterleave",
+    "pl_ldpc_qc_bp_plan_create", "pl_debug_ldpc_qc_bp_plan_probe",
 )
 PL_QUANT_LLR_F32 = 1  # pl_llr_quantize flag: llr_dev is float (else double)
 PL_RM_LLR_F32, PL_RM_OUT_F32, PL_RM_ACCUMULATE = 1, 2, 4  # pl_ldpc_rate_recover flags
@@ -85,6 +86,15 @@ class LdpcQcFixedPlanProbe(ctypes.Structure):
                [("digest", ctypes.c_uint64)]
 
 
+class LdpcQcBpPlanProbe(ctypes.Structure):
+    """pl_ldpc_qc_bp_plan_probe: the quasi-cyclic sum-product kernel's geometry."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("kernel", "z", "mb", "nb", "maxdc", "dcap", "mw", "fpw", "fpb", "threads",
+                                              "lds_bytes", "use_global")] + \
+               [("clip", ctypes.c_double)] + \
+               [(f, ctypes.c_int64) for f in ("state_bytes", "off_r", "table_len")] + \
+               [("digest", ctypes.c_uint64)]
+
+
 class QcEncoderProbe(ctypes.Structure):
     """pl_qc_encoder_probe: the quasi-cyclic encoder's structure, geometry and stream."""
     _fields_ = [(f, ctypes.c_int32) for f in ("g", "x", "a", "b", "subwave", "fpw", "fpb", "threads", "lds_bytes",
@@ -126,6 +136,9 @@ def _load(path=LIB_PATH):
     L.pl_ldpc_qc_fixed_plan_create.argtypes = [I32, I32, I32, P, P, I32, I32, I32, I32, I32, PP]
     L.pl_debug_ldpc_qc_fixed_plan_probe.argtypes = [I32, I32, I32, P, P, I32, I32, I32, I32, I32, I32,
                                                     ctypes.POINTER(LdpcQcFixedPlanProbe)]
+    L.pl_ldpc_qc_bp_plan_create.argtypes = [I32, I32, I32, P, P, I32, I32, D, PP]
+    L.pl_debug_ldpc_qc_bp_plan_probe.argtypes = [I32, I32, I32, P, P, I32, I32, D, I32,
+                                                 ctypes.POINTER(LdpcQcBpPlanProbe)]
     L.pl_ldpc_decode_i8.argtypes = [P, P, I64, I64, P, P, P, I64, P, I64, P]
     L.pl_llr_quantize.argtypes = [P, I32, I64, I64, I32, D, I32, P, I64, P]
     L.pl_ldpc_qc_encoder_create.argtypes = [I32, I32, I32, P, PP]
@@ -455,6 +468,22 @@ def qc_fixed_ldpc_plan(base: np.ndarray, Z: int, layer_order, max_iter: int, ear
                                            None if lo is None else lo.ctypes.data_as(ctypes.c_void_p), int(max_iter),
                                            int(bool(early_stop)), int(norm16), int(llr_max), int(msg_max),
                                            ctypes.byref(h)), "pl_ldpc_qc_fixed_plan_create")
+    return Plan(h)
+
+
+def qc_bp_ldpc_plan(base: np.ndarray, Z: int, layer_order, max_iter: int, early_stop: bool, clip: float) -> Plan:
+    """fp64 quasi-cyclic layered sum-product plan (pl_ldpc_qc_bp_plan_create); base and layer_order as
+    qc_ldpc_plan's."""
+    sh = np.ascontiguousarray(base, dtype=np.int32)
+    assert sh.ndim == 2, "base must be [mb, nb]"
+    lo = None if layer_order is None else np.ascontiguousarray(layer_order, dtype=np.int32).ravel()
+    assert lo is None or len(lo) == sh.shape[0], "layer_order must list the mb block rows"
+    require_gpu()
+    h = ctypes.c_void_p()
+    check(lib.pl_ldpc_qc_bp_plan_create(sh.shape[0], sh.shape[1], int(Z), sh.ctypes.data_as(ctypes.c_void_p),
+                                        None if lo is None else lo.ctypes.data_as(ctypes.c_void_p), int(max_iter),
+                                        int(bool(early_stop)), float(clip), ctypes.byref(h)),
+          "pl_ldpc_qc_bp_plan_create")
     return Plan(h)
 
 

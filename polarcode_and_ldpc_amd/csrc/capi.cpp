@@ -92,6 +92,10 @@ struct pl_plan {
     // that only pl_ldpc_decode_i8 decodes; its table buffer is the layer stream
     bool qc_fixed = false;
     pl::QcFixedGeom qfg{};
+    // fp64 quasi-cyclic layered sum-product (ldpc_qc_bp.hip): a layered plan (lms.n, lms.m set) decoded
+    // through the fp64 entry points; its table buffer is the layer stream
+    bool qc_bp = false;
+    pl::QcBpGeom qbg{};
     // workspace: bytes per unit (polar: one resident wave; LDPC global: one
     // frame), one buffer per stream (plans are shared across host threads that
     // use distinct streams; a decode only ever touches its stream's buffer)
@@ -460,6 +464,31 @@ extern "C" int pl_ldpc_qc_fixed_plan_create(int32_t mb, int32_t nb, int32_t z, c
     return PL_OK;
 }
 
+extern "C" int pl_ldpc_qc_bp_plan_create(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                         const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
+                                         double clip, pl_plan** out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    *out = nullptr;
+    // every argument check (ldpc_plan.cpp) comes before the first device call
+    pl::QcBpHostPlan hp;
+    const pl::PlanStatus st = pl::qc_bp_plan_build(mb, nb, z, shift, layer_order, max_iter, early_stop, clip,
+                                                   ldpc_env_options(), &hp);
+    if (st.code) return fail(st.code, st.msg);
+    PlanPtr plan;
+    if (int rc = ldpc_plan_upload(hp.tables, &plan)) return rc;
+    pl_plan* const p = plan.get();
+    p->layered = true;
+    p->qc_bp = true;
+    p->qbg = hp.geom;
+    p->lg.n = p->lms.n = hp.geom.n;
+    p->lg.m = p->lms.m = hp.geom.m;
+    const hipError_t e = pl::qc_prepare(p->qbg);
+    if (e != hipSuccess) return hipfail(e, "hipFuncSetAttribute");
+    p->ws_unit = p->qbg.use_global ? (size_t)p->qbg.state_bytes : 0;
+    *out = plan.release();
+    return PL_OK;
+}
+
 // The planner's decisions for a code, with no plan object and no device call.
 extern "C" int pl_debug_ldpc_plan_probe(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* col_idx,
                                         int32_t algo, int32_t max_iter, int32_t early_stop, double normalization,
@@ -539,6 +568,21 @@ extern "C" int pl_debug_ldpc_qc_fixed_plan_probe(int32_t mb, int32_t nb, int32_t
     return PL_OK;
 }
 
+extern "C" int pl_debug_ldpc_qc_bp_plan_probe(int32_t mb, int32_t nb, int32_t z, const int32_t* shift,
+                                              const int32_t* layer_order, int32_t max_iter, int32_t early_stop,
+                                              double clip, int32_t lms_global, pl_ldpc_qc_bp_plan_probe* out) {
+    if (!out) return fail(PL_EINVAL, "out is NULL");
+    pl::QcBpHostPlan hp;
+    const pl::PlanStatus st = pl::qc_bp_plan_build(mb, nb, z, shift, layer_order, max_iter, early_stop, clip,
+                                                   ldpc_options(0, 0, lms_global), &hp);
+    if (st.code) return fail(st.code, st.msg);
+    const pl::QcBpGeom& g = hp.geom;
+    *out = pl_ldpc_qc_bp_plan_probe{pl::qc_bp_kernel_code(g), g.z, g.mb, g.nb, g.maxdc, g.dcap, g.mw, g.fpw, g.fpb,
+                                    g.threads, g.lds_bytes, g.use_global, g.clip, g.state_bytes, g.off_r,
+                                    (int64_t)hp.tables.size(), pl::plan_tables_digest(hp.tables)};
+    return PL_OK;
+}
+
 // Polar workspace layout for a grid of `grid` resident wavefronts: a list
 // plan's NaN masks first (for its largest grid, so they stay in place, and
 // zero, from one decode to the next), then the tree / lane kernel's frame-group
@@ -600,10 +644,13 @@ static int lms_decode_impl(pl_plan* p, const IO* llr, int64_t batch, int64_t ld,
         } else if constexpr (std::is_same<IO, float>::value) {
             e = pl::qc_launch(p->qcg, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb, (unsigned char*)ws, s);
         } else {
-            e = p->qc ? pl::qc_launch(p->qcg, p->qc_f32, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
-                                      (unsigned char*)ws, s)
-                      : pl::lms_launch(p->lms, p->lmsd, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
-                                       (unsigned char*)ws, s);
+            if (p->qc_bp)
+                e = pl::qc_launch(p->qbg, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb, (unsigned char*)ws, s);
+            else
+                e = p->qc ? pl::qc_launch(p->qcg, p->qc_f32, p->d_ldpc, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
+                                          (unsigned char*)ws, s)
+                          : pl::lms_launch(p->lms, p->lmsd, llr + b0 * ld, ld, bo, io, po, ld_post, nb,
+                                           (unsigned char*)ws, s);
         }
         if (e == hipSuccess) return PL_OK;
         return hipfail(e, kFixed ? "fixed-point ldpc decode launch" : "layered ldpc decode launch");
@@ -1076,7 +1123,10 @@ extern "C" int pl_plan_get_info(const pl_plan* p, pl_plan_info* info) {
         info->kind = 1; info->n_in = p->lms.n; info->n_out = p->lms.n; info->list_size = 0;
         info->lds_bytes = p->lms.lds_bytes; info->fused_top = 0; info->frames_per_block = p->lms.fpb;
         info->reserved = pl::lms_kernel_code(p->lms);  // layered min-sum: 9 state in LDS, 10 in the workspace
-        if (p->qc || p->qc_fixed) {
+        if (p->qc_bp) {
+            info->lds_bytes = p->qbg.lds_bytes; info->frames_per_block = p->qbg.fpw * p->qbg.fpb;
+            info->reserved = pl::qc_bp_kernel_code(p->qbg);  // quasi-cyclic sum-product: 17 in LDS, 18 in the workspace
+        } else if (p->qc || p->qc_fixed) {
             const pl::QcMap& q = p->qc ? static_cast<const pl::QcMap&>(p->qcg) : p->qfg;
             info->lds_bytes = q.lds_bytes; info->frames_per_block = q.fpw * q.fpb;
             // quasi-cyclic layered min-sum: 11 state in LDS, 12 in the workspace; fp32 state: 13, 14; int8

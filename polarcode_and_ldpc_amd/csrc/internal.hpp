@@ -152,6 +152,11 @@ hipError_t qc_prepare(const QcFixedGeom& g);
 hipError_t qc_launch(const QcFixedGeom& g, const int32_t* tab, const int8_t* llr, int64_t ld, uint8_t* bits,
                      int32_t* iters, int8_t* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
 
+// fp64 sum-product (ldpc_qc_bp.hip): llr and post fp64, as the fp64 min-sum plan's
+hipError_t qc_prepare(const QcBpGeom& g);
+hipError_t qc_launch(const QcBpGeom& g, const int32_t* tab, const double* llr, int64_t ld, uint8_t* bits,
+                     int32_t* iters, double* post, int64_t ld_post, int64_t batch, unsigned char* work, hipStream_t s);
+
 // ---- the LLR quantiser (ldpc_qc_fixed.hip) ----
 // llr [batch][ldi] double, or float with f32; out int8 [batch][ldo]; chunks its launches itself
 hipError_t llr_quantize_launch(const void* llr, bool f32, int64_t ldi, int64_t batch, int n, double scale, int llr_max,

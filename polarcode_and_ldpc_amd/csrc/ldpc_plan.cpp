@@ -430,11 +430,12 @@ PlanStatus lms_plan_build(int m, int n, const int32_t* row_ptr, const int32_t* c
 
 // The fixed-point plan's three parameters (qc_fixed_plan_build); null for the floating-point plans.
 struct QcFixedParams { int norm16, llr_max, msg_max; };
+constexpr double kQcBpClipMax = 1048576.0;  // 2^20
 
 // The checks of a quasi-cyclic layered plan, in the order the header documents, then the layer stream.
 static PlanStatus qc_check_and_stream(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order,
                                       int max_iter, const QcFixedParams* fx, int* maxdc_out,
-                                      std::vector<int32_t>* tables) {
+                                      std::vector<int32_t>* tables, const double* bp_clip = nullptr) {
     if (mb < 1 || nb < 1 || z < 1 || !shift) return refuse(PL_EINVAL, "mb, nb and Z must be >= 1");
     if ((int64_t)nb * z > INT32_MAX || (int64_t)mb * z > INT32_MAX)
         return refuse(PL_EINVAL, "nb Z and mb Z must fit 32 bits");
@@ -475,9 +476,13 @@ static PlanStatus qc_check_and_stream(int mb, int nb, int z, const int32_t* shif
         if (fx->msg_max < 1 || fx->msg_max > 127)
             return refuse(PL_EINVAL, "msg_max = " + S(fx->msg_max) + " outside 1 .. 127");
     }
+    // the sum-product plan's clip (qc_bp_plan_build): finite, in (0, 2^20]; a NaN fails the first comparison
+    if (bp_clip && !(*bp_clip > 0.0 && *bp_clip <= kQcBpClipMax))
+        return refuse(PL_EINVAL, "clip = " + std::to_string(*bp_clip) + " outside (0, 2^20]");
     // max_iter == 0 evaluates no check, as in the layered plan
     if (deg1 && max_iter > 0)
-        return refuse(PL_EUNSUPPORTED, "min-sum on a degree-1 check (reference raises ValueError)");
+        return refuse(PL_EUNSUPPORTED, bp_clip ? "sum-product on a degree-1 check (the box-plus of no input)"
+                                               : "min-sum on a degree-1 check (reference raises ValueError)");
     if (maxdc >= (1 << 11)) return refuse(PL_EUNSUPPORTED, "check degree >= 2048");
     if (z > kQcMaxZ) return refuse(PL_EUNSUPPORTED, "Z > 1024");
 
@@ -564,6 +569,23 @@ PlanStatus qc_fixed_plan_build(int mb, int nb, int z, const int32_t* shift, cons
     g.off_p = (int64_t)4 * (mb * z) * mw;
     const int64_t state_bytes = (int64_t)ldpc_align16((size_t)g.off_p + (size_t)(nb * z));
     qc_map(g, mb, nb, z, max_iter, early_stop, maxdc, mw, state_bytes, opt.lms_global);
+    return {};
+}
+
+PlanStatus qc_bp_plan_build(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order, int max_iter,
+                            int early_stop, double clip, const LdpcPlanOptions& opt, QcBpHostPlan* out) {
+    int maxdc = 0;
+    const PlanStatus st = qc_check_and_stream(mb, nb, z, shift, layer_order, max_iter, nullptr, &maxdc, &out->tables,
+                                              &clip);
+    if (st.code) return st;
+    QcBpGeom& g = out->geom;
+    g = QcBpGeom{};
+    g.clip = clip;
+    const size_t blocks = (out->tables.size() - 2 * (size_t)mb) / 2;  // the stream is 2 words a layer and 2 a block
+    g.off_r = (int64_t)ldpc_align16((size_t)8 * ((size_t)nb * z));
+    const int64_t state_bytes = (int64_t)ldpc_align16((size_t)g.off_r + (size_t)8 * z * blocks);
+    qc_map(g, mb, nb, z, max_iter, early_stop, maxdc, 0, state_bytes, opt.lms_global);
+    g.dcap = 0;  // the rule keeps no input in registers: the two-pass instances only
     return {};
 }
 

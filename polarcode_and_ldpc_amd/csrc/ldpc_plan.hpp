@@ -260,6 +260,28 @@ PlanStatus qc_fixed_plan_build(int mb, int nb, int z, const int32_t* shift, cons
                                int early_stop, int norm16, int llr_max, int msg_max, const LdpcPlanOptions& opt,
                                QcFixedHostPlan* out);
 
+// ---- fp64 quasi-cyclic layered sum-product (ldpc_qc_bp.hip) ----
+// The definition: include/polarldpc.h, pl_ldpc_qc_bp_plan_create.  Mapping and layer stream are
+// qc_plan_build's.  State per frame, all of it in LDS or all of it in the frame's workspace slice:
+//   at 0      P[n] f64
+//   at off_r = align16(8 n)   R as [blocks][z] f64: edge j of a layer is slot (blocks of the earlier
+//             layers of the stream) + j, its check r element slot z + r -- consecutive lanes,
+//             consecutive doubles
+//   state_bytes = align16(off_r + 8 z blocks)
+struct QcBpGeom : QcMap {  // mw: 0 (no check words); dcap: 0 (the rule keeps no input in registers)
+    double clip;           // the clamp of P on load and of every q
+    int64_t off_r;
+};
+inline int qc_bp_kernel_code(const QcBpGeom& g) { return g.use_global ? 18 : 17; }
+struct QcBpHostPlan {
+    QcBpGeom geom{};
+    std::vector<int32_t> tables;  // QcHostPlan::tables: the same stream for the same base matrix
+};
+// pl_ldpc_qc_bp_plan_create's arguments.  qc_plan_build's checks in its order, with clip finite and in
+// (0, 2^20] (PL_EINVAL) behind the layer_order check and in front of the PL_EUNSUPPORTED ones.
+PlanStatus qc_bp_plan_build(int mb, int nb, int z, const int32_t* shift, const int32_t* layer_order, int max_iter,
+                            int early_stop, double clip, const LdpcPlanOptions& opt, QcBpHostPlan* out);
+
 // ---- quasi-cyclic encoder from the base matrix (ldpc_qc_encode.hip) ----
 // The supported structure and the encoding steps: include/polarldpc.h,
 // pl_ldpc_qc_encoder_create.  kb = nb - mb message block columns, then mb parity

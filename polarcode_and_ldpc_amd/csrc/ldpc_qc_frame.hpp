@@ -1,6 +1,6 @@
-// The frame skeleton of the quasi-cyclic layered min-sum decoders on gfx950
-// (MI355X): everything ldpc_qc_layered.hip (fp64, fp32) and ldpc_qc_fixed.hip
-// (int8) do alike -- lanes to (frame, check), the state's home, the load of P,
+// The frame skeleton of the quasi-cyclic layered decoders on gfx950 (MI355X):
+// everything ldpc_qc_layered.hip (min-sum, fp64 and fp32), ldpc_qc_fixed.hip
+// (min-sum, int8) and ldpc_qc_bp.hip (sum-product, fp64) do alike -- lanes to (frame, check), the state's home, the load of P,
 // the walk over the layer stream, the syndrome pass, the stop votes, the hard
 // decision and the stores -- and the choice and launch of an instance.  Device
 // code; each .hip instantiates its own kernels from it.
@@ -33,8 +33,12 @@
 //                    one layered update of check c = (block row) Z + r of degree d >= 2,
 //                    pr its d (block column, shift) pairs; first: the check's state holds
 //                    nothing yet
+//   A rule that declares kEdgeOffset = true takes one more argument behind first: the number of
+//                    blocks in the earlier layers of the stream (where a per-edge state of the layer begins)
 // In all of them a bit is 1 and a parity term is set where P[v] <= 0, and post is (IO)P[v].
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 #include "internal.hpp"
 #include "ldpc_lms_check.hpp"  // lms_sync, lms_wg_any
@@ -46,6 +50,18 @@ PL_DEV int qc_var(int col, int s, int r, int z) {
     const int t = r + s;
     return col * z + (t >= z ? t - z : t);
 }
+
+// whether a rule asks for the layer's edge offset (Rule::kEdgeOffset)
+template <class Rule, class = void>
+struct QcRuleEdgeOffset { static constexpr bool value = false; };
+template <class Rule>
+struct QcRuleEdgeOffset<Rule, std::void_t<decltype(Rule::kEdgeOffset)>> {
+    static constexpr bool value = Rule::kEdgeOffset;
+};
+// the stream walk's count of the blocks behind it: an int for the rules that ask, nothing for the others
+struct QcNoEdgeOffset {
+    PL_DEV void operator+=(int) {}
+};
 
 template <class Rule, int DCAP, bool SUBWAVE, bool GLOBAL>
 __global__ void __launch_bounds__(SUBWAVE ? 256 : 1024)
@@ -93,12 +109,18 @@ qc_frame_kernel(typename Rule::Geom g, const int32_t* __restrict__ tab, const ty
     int done = g.max_iter;
     for (int it = 0; it < g.max_iter; ++it) {
         const int32_t* t = tab;
+        std::conditional_t<QcRuleEdgeOffset<Rule>::value, int, QcNoEdgeOffset> e0{};  // blocks of the layers walked
         for (int l = 0; l < g.mb; ++l) {
             const int i = t[0], d = t[1];
             if (d > 0) {  // the same in every lane
-                if (live) rule.template update<DCAP>(g, t + 2, d, r, i * z + r, it == 0);
+                if constexpr (QcRuleEdgeOffset<Rule>::value) {
+                    if (live) rule.template update<DCAP>(g, t + 2, d, r, i * z + r, it == 0, e0);
+                } else {
+                    if (live) rule.template update<DCAP>(g, t + 2, d, r, i * z + r, it == 0);
+                }
                 lms_sync<SUBWAVE>();
             }
+            e0 += d;
             t += 2 + 2 * d;
         }
         if (g.early_stop) {

@@ -15,7 +15,8 @@ max_iterations, errors over the k message positions.  LDPC frames use the
 all-zero codeword (BP is codeword-symmetric) or, on request, random messages
 through a device encoder; polar frames use random messages through the device
 encoder.  simulate_qc_ldpc is the same for a quasi-cyclic code given by its base
-matrix (layered min-sum, fp64, fp32 or int8 fixed point; codewords from QCLDPCEncoder).
+matrix (layered min-sum, fp64, fp32 or int8 fixed point, or layered sum-product;
+codewords from QCLDPCEncoder).
 """
 from __future__ import annotations
 
@@ -161,7 +162,8 @@ def simulate_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: in
 def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors: int, base, Z: int,
                      max_iter: int = 20, normalization: float = 0.75, dtype=np.float64, batch: int = 65536,
                      seed: int = 0, group=None, random_codewords: bool = False, log_path=None, rate_match=None,
-                     fixed=None, modulation=None, interleaver=None, fading=None):
+                     fixed=None, modulation=None, interleaver=None, fading=None, algo: str = "minsum",
+                     clip: float = 64.0):
     """simulate_ldpc for the quasi-cyclic code (base, Z): QCLayeredMSDecoder (layered
     normalised min-sum, early stop, state in `dtype`) on frames of the all-zero
     codeword or, random_codewords, of random messages encoded on the device from
@@ -186,15 +188,26 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
     interleaver: as simulate_polar's (the transmitted length is the matcher's E, or n);
     ldpc_round_fn's interleaver, which needs random_codewords.
 
-    fading: as simulate_polar's (ldpc_round_fn's fading)."""
+    fading: as simulate_polar's (ldpc_round_fn's fading).
+
+    algo: "minsum" (the default: the decoders above), or "bp": the layered sum-product
+    decoder QCLayeredBPDecoder with the clamp `clip` instead (fp64; `normalization`,
+    `dtype` are not used and `fixed` must be None).  "algo" and "clip" enter the log's
+    run key only with "bp"."""
     import torch
-    from ..ldpc.decoder import QCFixedMSDecoder, QCLayeredMSDecoder
+    from ..ldpc.decoder import QCFixedMSDecoder, QCLayeredBPDecoder, QCLayeredMSDecoder
     from ..ldpc.encoder import QCLDPCEncoder
     base = np.asarray(base, dtype=np.int64)
     more = {}
     if fixed is not None:
         fixed = (float(fixed[0]), int(fixed[1]), int(fixed[2]))
         more["fixed"] = list(fixed)
+    if algo not in ("minsum", "bp"):
+        raise ValueError("simulate_qc_ldpc: algo must be 'minsum' or 'bp', not %r" % (algo,))
+    if algo == "bp":
+        if fixed is not None:
+            raise ValueError("simulate_qc_ldpc: algo='bp' is fp64; it does not go with fixed=")
+        more["algo"], more["clip"] = "bp", float(clip)
     kw = {}
     if modulation is not None:
         more["modulation"] = modulation.m
@@ -209,13 +222,15 @@ def simulate_qc_ldpc(snr_db_range: Sequence[float], num_frames: int, max_errors:
             more["interleave"] = kw["interleaver"].key
 
     def make_decoder(b):
+        if algo == "bp":
+            return QCLayeredBPDecoder(b, Z, max_iter=max_iter, early_stop=True, clip=clip)
         if fixed is None:
             return QCLayeredMSDecoder(b, Z, max_iter=max_iter, normalization=normalization, early_stop=True, dtype=dtype)
         return QCFixedMSDecoder(b, Z, max_iter=max_iter, normalization=normalization, early_stop=True,
                                 llr_scale=fixed[0], llr_max=fixed[1], msg_max=fixed[2])
 
     def dtype_name(dec):
-        return "int8" if fixed is not None else np.dtype(dec.dtype).name
+        return "int8" if fixed is not None else np.dtype(getattr(dec, "dtype", np.float64)).name
     if rate_match is not None:
         from ..ldpc.ratematch import QCRateMatcher
         rm = QCRateMatcher(base, Z, **rate_match) if isinstance(rate_match, dict) else QCRateMatcher(base, Z, *rate_match)
@@ -312,6 +327,10 @@ def main(argv=None):
     ap.add_argument("--fixed", default=None,
                     help="--code qcldpc: scale,llr_max,msg_max, the int8 fixed-point decoder (ldpc.QCFixedMSDecoder) "
                          "instead of the floating one; --dtype is then not used")
+    ap.add_argument("--qc-algo", choices=["minsum", "bp"], default="minsum",
+                    help="--code qcldpc: the check rule, normalised min-sum (the default) or sum-product "
+                         "(ldpc.QCLayeredBPDecoder, fp64; --norm, --dtype are then not used)")
+    ap.add_argument("--clip", type=float, default=64.0, help="--qc-algo bp: the clamp of the messages")
     ap.add_argument("--modulation", choices=["qpsk", "16qam", "64qam", "256qam"], default=None,
                     help="--code polar, qcldpc: Gray-mapped QAM (channel.QAMModem) instead of BPSK; --snr is then Es/N0 "
                          "per QAM symbol; qcldpc needs --ldpc-codewords random")
@@ -397,6 +416,10 @@ def main(argv=None):
             if len(fx) != 3:
                 ap.error("--fixed takes scale,llr_max,msg_max")
             more["fixed"] = (float(fx[0]), int(fx[1]), int(fx[2]))
+        if a.qc_algo == "bp":
+            if a.fixed is not None:
+                ap.error("--qc-algo bp does not go with --fixed")
+            more.update(algo="bp", clip=a.clip)
         ber, fer, pts = simulate_qc_ldpc(snr, a.frames, a.max_errors, base, q[2], max_iter=a.max_iter,
                                          normalization=a.norm, dtype=np.dtype(a.dtype).type, batch=a.batch,
                                          seed=a.seed, random_codewords=a.ldpc_codewords == "random", log_path=a.log,

@@ -435,7 +435,8 @@ def ldpc_round_fn(decoder, seed: int = 0, info_bits: Optional[int] = None, encod
                   modulation=None, interleaver=None, fading=None):
     """Round function for BPDecoder / MSDecoder / LayeredMSDecoder (any decoder
     with `.plan`, `.n` and `.m`).  A QCFixedMSDecoder takes the same chain: the
-    channel LLRs (and the recovery) stay fp64 and the decoder quantises them.
+    channel LLRs (and the recovery) stay fp64 and the decoder quantises them.  A
+    QCLayeredBPDecoder (sum-product, fp64) takes it as the fp64 min-sum decoders do.
 
     encoder None: the all-zero codeword (BP and min-sum are codeword-symmetric);
     errors over the first `info_bits` positions, like ber_simulation.py:265-269

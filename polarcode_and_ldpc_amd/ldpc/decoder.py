@@ -6,7 +6,8 @@ src/ldpc/decoder.py (BPDecoder :11-205, MSDecoder :208-355), plus
 LayeredMSDecoder (ldpc_layered.hip) is a build-defined extension: the serial
 schedule with posterior LLR output; QCLayeredMSDecoder (ldpc_qc_layered.hip) is
 the same decoder for a quasi-cyclic code given by its base matrix, and
-QCFixedMSDecoder (ldpc_qc_fixed.hip) its int8 fixed-point counterpart.
+QCFixedMSDecoder (ldpc_qc_fixed.hip) its int8 fixed-point counterpart;
+QCLayeredBPDecoder (ldpc_qc_bp.hip) is the sum-product decoder on the same schedule.
 """
 from __future__ import annotations
 
@@ -408,3 +409,54 @@ class QCFixedMSDecoder(LayeredMSDecoder):
     def __repr__(self) -> str:
         return (f"QCFixedMSDecoder(n={self.n}, m={self.m}, Z={self.Z}, max_iter={self.max_iter}, "
                 f"norm={self.norm16}/16, llr_scale={self.llr_scale}, llr_max={self.llr_max}, msg_max={self.msg_max})")
+
+
+class QCLayeredBPDecoder(LayeredMSDecoder):
+    """Layered sum-product (belief propagation) decoder for a quasi-cyclic code given
+    by its base matrix (ldpc_qc_bp.hip), fp64.  `base`, `Z` and `layer_order`, the
+    schedule, the stop rule and the hard decision as QCLayeredMSDecoder's; the check
+    rule is the exact box-plus, evaluated as a forward / backward recursion with
+    glibc's expm1 and log1p, and every variable-to-check message is clamped to
+    +-`clip` (finite, 0 < clip <= 2**20; ValueError otherwise).  The definition is
+    printed in include/polarldpc.h at pl_ldpc_qc_bp_plan_create; bits, iteration
+    counts and posteriors equal a NumPy restatement of it bit for bit.  NaN LLRs are
+    erasures and +-inf are +-clip, so every posterior is finite
+    (|P| <= 2 clip + ln 2)."""
+
+    def __init__(self, base: np.ndarray, Z: int, max_iter: int = 50, early_stop: bool = True, layer_order=None,
+                 clip: float = 64.0):
+        clip = float(clip)
+        if not 0.0 < clip <= 2.0 ** 20:  # a NaN fails the comparison
+            raise ValueError("QCLayeredBPDecoder: clip must be finite with 0 < clip <= 2**20, not %r" % (clip,))
+        self._algo = _native.PL_LDPC_LMS
+        self.base = np.array(base, dtype=np.int64)
+        assert self.base.ndim == 2, "base must be [mb, nb]"
+        self.Z = int(Z)
+        self.mb, self.nb = self.base.shape
+        self.m, self.n = self.mb * self.Z, self.nb * self.Z
+        self.max_iter = max_iter
+        self.early_stop = early_stop
+        self.clip = clip
+        self.layer_order = None if layer_order is None else [int(i) for i in layer_order]
+        self.check_degrees = np.repeat((self.base >= 0).sum(axis=1), self.Z)
+        self.var_neighbors = None
+        self._plan = None
+        self._H = None
+
+    H = QCLayeredMSDecoder.H
+    layers = QCLayeredMSDecoder.layers
+
+    @property
+    def plan(self):
+        if self._plan is None:
+            self._plan = _native.qc_bp_ldpc_plan(self.base, self.Z, self.layer_order, self.max_iter, self.early_stop,
+                                                 self.clip)
+        return self._plan
+
+    def _check_runnable(self):
+        if self.max_iter > 0 and np.any(self.check_degrees == 1):
+            raise ValueError("sum-product on a degree-1 check: the box-plus of no input")
+
+    def __repr__(self) -> str:
+        return (f"QCLayeredBPDecoder(n={self.n}, m={self.m}, Z={self.Z}, max_iter={self.max_iter}, "
+                f"clip={self.clip})")

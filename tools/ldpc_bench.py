@@ -1,7 +1,7 @@
 """LDPC decode kernel timing (diagnostic): HIP events around repeated launches.
 
-usage: python tools/ldpc_bench.py [--batch 65536] [--algo bp,ms,lms,qclms,qclms32,qclms8] [--n 504] [--seed 3]
-                                  [--fixed 4,31,31]
+usage: python tools/ldpc_bench.py [--batch 65536] [--algo bp,ms,lms,qclms,qclms32,qclms8,qcbp] [--n 504] [--seed 3]
+                                  [--fixed 4,31,31] [--clip 64]
                                   [--qc mb,nb,Z,dv,seed] [--qc-encodable]
                                   [--random-codewords] [--max-iter 20] [--no-early-stop]
                                   [--snr 3.0] [--valid] [--norm 0.75] [--reps 5] [--rounds 3]
@@ -21,6 +21,8 @@ compared: `frames_differ_from_qclms` counts the frames whose bits differ.
 `qclms8` is QCFixedMSDecoder (int8 fixed point, --fixed scale,llr_max,msg_max) on the
 same device frames, quantised once by the decoder's own kernel outside the timed
 region; reported like qclms32, with `frames_differ_from_qclms32` when both run.
+`qcbp` is QCLayeredBPDecoder (layered sum-product, fp64, --clip) on the same fp64 frames;
+another decoder again, reported with `frames_differ_from_qclms` when both run.
 --qc-encodable: the code qc_encodable_base(mb, nb, Z, dv, seed) instead, whose parity
 part QCLDPCEncoder can encode from; without it --qc means what it always meant.
 --random-codewords (needs --qc-encodable): the frames carry random messages encoded on
@@ -37,7 +39,7 @@ import numpy as np, torch
 from polarcode_and_ldpc_amd.channel import AWGNChannel
 from polarcode_and_ldpc_amd import _native
 from polarcode_and_ldpc_amd.ldpc import (BPDecoder, MSDecoder, LayeredMSDecoder, LDPCEncoder, QCLDPCEncoder,
-                                         QCFixedMSDecoder, QCLayeredMSDecoder, qc_block_layers, qc_encodable_base, qc_random_base,
+                                         QCFixedMSDecoder, QCLayeredBPDecoder, QCLayeredMSDecoder, qc_block_layers, qc_encodable_base, qc_random_base,
                                          qc_to_csr, regular_construction)
 
 ap = argparse.ArgumentParser()
@@ -55,6 +57,7 @@ ap.add_argument("--qc-encodable", action="store_true", help="--qc builds qc_enco
 ap.add_argument("--random-codewords", action="store_true",
                 help="--qc-encodable: random codewords from QCLDPCEncoder instead of the all-zero one")
 ap.add_argument("--fixed", default="4,31,31", help="qclms8: llr_scale,llr_max,msg_max")
+ap.add_argument("--clip", type=float, default=64.0, help="qcbp: the clamp of the messages")
 ap.add_argument("--reps", type=int, default=5, help="launches per timed round")
 ap.add_argument("--rounds", type=int, default=3)
 a = ap.parse_args()
@@ -115,10 +118,12 @@ def make(spec):
             fs, fl, fm = a.fixed.split(",")
             return QCFixedMSDecoder(qc, Z, max_iter=mi, normalization=a.norm, early_stop=es, llr_scale=float(fs),
                                     llr_max=int(fl), msg_max=int(fm))
+        if name == "qcbp":
+            return QCLayeredBPDecoder(qc, Z, max_iter=mi, early_stop=es, clip=a.clip)
         if name == "lms":
             return GenericOnQc(mi)
-        raise SystemExit("--qc takes --algo lms, qclms, qclms32 and qclms8 only, not %r" % spec)
-    if name in ("qclms", "qclms32", "qclms8"):
+        raise SystemExit("--qc takes --algo lms, qclms, qclms32, qclms8 and qcbp only, not %r" % spec)
+    if name in ("qclms", "qclms32", "qclms8", "qcbp"):
         raise SystemExit("--algo %s needs --qc mb,nb,Z,dv,seed" % name)
     if name == "bp":
         return BPDecoder(H, max_iter=mi, early_stop=es)
@@ -168,6 +173,9 @@ if qc is not None:  # the two decoders are one definition: equal on the timed fr
     if "qclms" in names and "qclms32" in names:
         (b0, _), (b1, _) = results[names["qclms"]], results[names["qclms32"]]
         stats[specs.index(names["qclms32"])]["frames_differ_from_qclms"] = int((b0 != b1).any(dim=1).sum())
+    if "qclms" in names and "qcbp" in names:
+        (b0, _), (b1, _) = results[names["qclms"]], results[names["qcbp"]]
+        stats[specs.index(names["qcbp"])]["frames_differ_from_qclms"] = int((b0 != b1).any(dim=1).sum())
     if "qclms32" in names and "qclms8" in names:
         (b0, _), (b1, _) = results[names["qclms32"]], results[names["qclms8"]]
         stats[specs.index(names["qclms8"])]["frames_differ_from_qclms32"] = int((b0 != b1).any(dim=1).sum())
